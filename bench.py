@@ -10,7 +10,14 @@ The corpus is SURVEY.md 8(d)'s mixed generator set (wordsalad, xorshift32,
 structured int32 deltas, cycling per 4 MiB window), generated on the device.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--size BYTES] [--level L]
-                  [--mode weak|c3]
+                  [--mode weak|c3] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps, checks the last step's
+round trip and prints the result line.  `--full` adds every leg beside the
+headline (below).  `--dump-outputs DIR` writes what the last timed step
+returned (stream length and bytes, inflated length and bytes; a fixed seeded
+sample of the large arrays) as DIR/<name>.npy; the corpus is seeded, so two
+runs with the same arguments dump the outputs of identical inputs.
 
 Processes: one per GPU.  Under torch.distributed.run (WORLD_SIZE set) every
 process is one rank.  `--gpus N` without a launcher makes this process a
@@ -35,7 +42,9 @@ Modes:
 
 Extra fields: `roofline` for the dominant kernel (deflate's match_kernel,
 the LZ77 match finder; algorithmic bytes = N input bytes per launch, SURVEY.md
-8(d), timed with HIP events on its launch stream), `cpu_baseline` (the oracle
+8(d), timed with HIP events on its launch stream, inside the timed steps);
+with `--full` also the round-trip check before the warm-up (a plain weak-mode
+run checks the last timed step's output instead), `cpu_baseline` (the oracle
 -- the C restatement of the reference's RawDeflate + RawInflate -- on a
 bounded sample on 16 threads, one-core figure beside it, rank 0, N = 1
 only), the per-generator compression ratio of
@@ -73,10 +82,16 @@ def parse_args(argv=None):
     ap.add_argument("--size", type=int, default=None, help="bytes (default 1 GiB; 8 GiB in c3 mode)")
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--mode", choices=["weak", "c3"], default="weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-api", action="store_true", help="skip the host-buffer (PCIe-inclusive) round trip")
-    ap.add_argument("--no-node", action="store_true", help="skip the Node (N-API facade) round trip")
-    ap.add_argument("--no-per-generator", action="store_true", help="skip the per-generator rates")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: the untimed round-trip check before the warm-up, "
+                         "cpu_baseline / ratio_vs_ref, api, api_node, per_generator (rank 0, --gpus 1, weak mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step returned as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-api", action="store_true",
+                    help="with --full: skip the host-buffer (PCIe-inclusive) round trip")
+    ap.add_argument("--no-node", action="store_true", help="with --full: skip the Node (N-API facade) round trip")
+    ap.add_argument("--no-per-generator", action="store_true", help="with --full: skip the per-generator rates")
     a = ap.parse_args(argv)
     if a.size is None:
         a.size = (8 << 30) if a.mode == "c3" else (1 << 30)
@@ -373,6 +388,37 @@ def per_generator(d_in, n, level, dplan, iplan, d_c, d_out, zt):
     return out
 
 
+DUMP_SAMPLE = 4 << 20  # elements per dumped array: 16 MiB as float32, two arrays per rank
+
+
+def dump_outputs(path, rank, world, d_c, clen, d_out, olen):
+    """--dump-outputs: what the last timed step returned to its caller, as
+    float32 / float64 .npy files under `path` -- `lengths` (stream bytes,
+    inflated bytes; -1 where the mode runs no inflate), `deflate_stream` (the
+    stream's bytes) and `inflate_output` (the bytes inflated from it).  An
+    array of more than DUMP_SAMPLE bytes is dumped as the bytes at
+    DUMP_SAMPLE sorted positions drawn by a seeded generator from
+    [0, length): the same positions in every run over an output of the same
+    length, and a stream of another length is told apart by `lengths`."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+
+    def sample(buf, length):
+        if length > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(20240611).integers(0, length, size=DUMP_SAMPLE))
+            return buf.index_select(0, torch.from_numpy(idx).to(buf.device)).cpu().numpy().astype(np.float32)
+        return buf[:length].cpu().numpy().astype(np.float32)
+
+    np.save(os.path.join(path, f"lengths{tag}.npy"),
+            np.array([clen, -1 if olen is None else olen], dtype=np.float64))
+    np.save(os.path.join(path, f"deflate_stream{tag}.npy"), sample(d_c, clen))
+    if olen is not None:
+        np.save(os.path.join(path, f"inflate_output{tag}.npy"), sample(d_out, olen))
+
+
 # ---------------------------------------------------------------- ranks
 def run_rank(args):
     import torch
@@ -430,9 +476,13 @@ def run_rank(args):
             return clen, None
         return clen, inflate(clen)
 
-    # correctness of the measured path (untimed): the round trip is exact
-    clen = deflate()
-    if n:
+    # correctness of the measured path (untimed): the round trip is exact.
+    # A plain weak-mode run checks the last timed step's own output instead
+    # (below), which costs no step of its own
+    precheck = args.full or args.mode == "c3"
+    if precheck:
+        clen = deflate()
+    if precheck and n:
         slen = clen
         if not last:  # close this shard's stream with an empty final fixed block (03 00)
             d_c[clen:clen + 2] = torch.tensor([3, 0], dtype=torch.uint8, device="cuda")
@@ -459,6 +509,10 @@ def run_rank(args):
     elapsed = time.perf_counter() - t0
     kt = zt.timing_read()
     zt.timing_enable(False)
+    if not precheck and n and (olen != n or not torch.equal(d_out[:n], d_in[:n])):
+        raise SystemExit(f"bench: round trip mismatch on rank {rank}")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, d_c, clen, d_out, olen)
     elapsed = max_over_ranks(elapsed, pg)
     total_c = sum_over_ranks(clen, pg)
 
@@ -507,7 +561,7 @@ def run_rank(args):
         line["inflate_kernel_ms"] = round(inf_ms, 3)
         line["inflate_tokenize_ms"] = round(tok_ms, 3)
         line["inflate_GiBps"] = round(n / (inf_ms * 1e-3) / 2**30, 3) if inf_ms else None
-    if rank == 0 and world == 1 and args.mode == "weak":
+    if args.full and rank == 0 and world == 1 and args.mode == "weak":
         if not args.no_cpu_baseline and n >= 3 * WINDOW:
             cb, ratios = cpu_baseline(d_in, args.level, zt)
             line["cpu_baseline"] = cb

@@ -123,6 +123,45 @@ def test_bench_spawns_ranks():
     assert line["config"]["bytes_total"] == 2 * (64 << 20)
 
 
+FULL_LEGS = ["cpu_baseline", "ratio_vs_ref", "api", "api_node", "per_generator"]
+
+
+def test_bench_plain_run_dumps_last_step(zt, tmp_path):
+    """A plain run carries the headline fields and none of the --full legs;
+    --dump-outputs writes what its last timed step returned: the stream
+    (which inflates to the seeded corpus) and the inflated bytes (the corpus
+    itself), whole at this size, as float32, with their lengths as float64."""
+    import numpy as np
+    import torch
+
+    n = (3 << 20) + 123
+    line = _bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--size", str(n), "--dump-outputs", str(tmp_path))
+    assert line["steps"] == 2 and line["unit"] == "GiB/s" and line["higher_is_better"] is True
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - n / 2**30 / (line["ms_per_step"] * 1e-3)) <= 0.01 * line["value"]
+    assert not [k for k in FULL_LEGS if k in line]
+    assert sorted(os.listdir(tmp_path)) == ["deflate_stream.npy", "inflate_output.npy", "lengths.npy"]
+    lengths = np.load(tmp_path / "lengths.npy")
+    stream = np.load(tmp_path / "deflate_stream.npy")
+    out = np.load(tmp_path / "inflate_output.npy")
+    assert lengths.dtype == np.float64 and stream.dtype == np.float32 and out.dtype == np.float32
+    assert lengths.tolist() == [len(stream), n] and len(out) == n
+    d = torch.empty(n + 64, dtype=torch.uint8, device="cuda")
+    zt.synth_dev("mixed", 11, d.data_ptr(), n)
+    want = d[:n].cpu().numpy()
+    assert np.array_equal(out, want.astype(np.float32))
+    g, ip = zt.inflate_raw(stream.astype(np.uint8).tobytes())
+    assert ip == len(stream) and g == want.tobytes()
+
+
+def test_bench_full_keeps_every_leg():
+    """--full adds the legs beside the headline (Node's is switched off here)."""
+    line = _bench("--gpus", "1", "--steps", "1", "--warmup", "0", "--size", str(16 << 20), "--full", "--no-node")
+    assert [k for k in FULL_LEGS if k in line] == ["cpu_baseline", "ratio_vs_ref", "api", "per_generator"]
+    assert line["cpu_baseline"]["value"] > 0 and line["api"]["roundtrip_GiBps"] > 0
+    assert set(line["per_generator"]) >= {"wordsalad", "structured", "xorshift32"}
+
+
 def test_bench_c3_mode_two_ranks():
     line = _bench("--gpus", "2", "--mode", "c3", "--steps", "1", "--warmup", "0", "--size", str((96 << 20) + 4097))
     assert line["n_gpus"] == 2 and line["scaling"] == "strong"

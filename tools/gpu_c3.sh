@@ -8,5 +8,5 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_c3.py -x -v --timeout 300 -
 tail -3 gpurun_out/${TAG}_t.log
 timeout -k 10 300 python bench.py --mode c3 --steps 3 --warmup 1 > gpurun_out/${TAG}_bench_c3.log 2>&1
 tail -1 gpurun_out/${TAG}_bench_c3.log
-timeout -k 10 300 python bench.py > gpurun_out/${TAG}_bench.log 2>&1
-tail -1 gpurun_out/${TAG}_bench.log
+# the headline line with every leg (bench.py --full): the runner's bench step, log in its TAG folder
+tools/gpu_run.sh $TAG bench

@@ -12,8 +12,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 tail -1 gpurun_out/${TAG}_pytest.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1
 tail -1 gpurun_out/${TAG}_smoke.log
-timeout -k 10 600 python bench.py > gpurun_out/${TAG}_bench.log 2>&1
-tail -1 gpurun_out/${TAG}_bench.log
+# the bench line with every leg (bench.py --full): the runner's bench step, log in its TAG folder
+tools/gpu_run.sh $TAG bench
 # the 16-window ratio gate of this build (one gate log per checkpoint)
 timeout -k 10 300 python3 tools/ratio_gate.py > gpurun_out/${TAG}_gate.log 2>&1
 tail -1 gpurun_out/${TAG}_gate.log

@@ -8,8 +8,8 @@
 #   pytest            full -m gpu suite                       (pytest.log)
 #   pytest:EXPR       -m gpu suite restricted by -k EXPR      (pytest.log)
 #   smoke             __graft_entry__.smoke()                 (smoke.log)
-#   bench             python bench.py (defaults)              (bench.log)
-#   benchq            bench.py --steps 5 --no-cpu-baseline    (bench.log)
+#   bench             python bench.py --full (every leg)      (bench.log)
+#   benchq            bench.py --full --steps 5 --no-cpu-baseline (bench.log)
 #   gate              16-window ratio gate                    (gate.log)
 #   prof              rocprof kernel stats of 3 bench steps   (kernel_stats.csv)
 #   c1 / c2 / c4      rocprof kernel stats of C1 / C2 / C4    (cN_kernel_stats.csv)
@@ -54,8 +54,8 @@ for step in "$@"; do
     pytest) timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }; tail -1 $O/pytest.log ;;
     pytest:*) timeout -k 10 600 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -k "${step#pytest:}" > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }; tail -1 $O/pytest.log ;;
     smoke) timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log ;;
-    bench) timeout -k 10 600 python3 bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log ;;
-    benchq) timeout -k 10 300 python3 bench.py --steps 5 --no-cpu-baseline > $O/bench.log 2>&1; tail -1 $O/bench.log ;;
+    bench) timeout -k 10 600 python3 bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log ;;
+    benchq) timeout -k 10 300 python3 bench.py --full --steps 5 --no-cpu-baseline > $O/bench.log 2>&1; tail -1 $O/bench.log ;;
     gate) timeout -k 10 300 python3 tools/ratio_gate.py > $O/gate.log 2>&1; tail -2 $O/gate.log ;;
     prof) prof bench 300 -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-api --no-per-generator ;;
     c1) prof c1 180 -- python3 $R/tools/ck_time.py ;;
