@@ -1,5 +1,5 @@
 // zip_api.cpp -- Zip / Unzip archives over the batch engine (SURVEY.md 8(f)
-// row 3; include/zt.h).  No ZipCrypto.
+// row 3; include/zt.h), with ZipCrypto passwords (include/zt_zipcrypto.h).
 //
 // zt_zip_compress follows src/Zip.ts:117-372: local file headers with the data,
 // then the central directory and its end record, laid out byte for byte as the
@@ -11,6 +11,11 @@
 // checks and messages, and every DEFLATE member is inflated in one batch (the
 // two-phase batch inflate of inflate_api.cpp); `verify` checks each CRC-32 on
 // the GPU.
+//
+// Passwords (src/Zip.ts:152-187, src/Unzip.ts:263-282; zipcrypto.hip): Zip
+// encrypts header12 | body of every protected entry in one batch; Unzip
+// decrypts the protected entries in place in the archive's device copy (the
+// caller's buffer is never written) before the batch inflate reads them.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -18,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "zipcrypto.h"
 #include "zt_internal.h"
 
 namespace zt {
@@ -58,12 +64,15 @@ struct BS {
 
 using namespace zt;
 
-extern "C" {
+namespace {
 
-int zt_zip_compress(const uint8_t *const *in, const size_t *n, const zt_zip_file *files, size_t count,
-                    const uint8_t *comment, size_t comment_len, uint8_t **out, size_t *out_len) {
+int zip_compress_impl(const uint8_t *const *in, const size_t *n, const zt_zip_file *files, const zt_zip_crypt *crypt,
+                      size_t count, const uint8_t *comment, size_t comment_len, uint8_t **out, size_t *out_len) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (count && (!in || !n || !files)) return set_error(ZT_E_ARG, "null argument");
+  if (crypt)
+    for (size_t i = 0; i < count; ++i)
+      if (crypt[i].password_len && !crypt[i].password) return set_error(ZT_E_ARG, "null password");
   // DEFLATE members: one batch per deflate setting (normally one)
   std::vector<uint8_t *> body(count, nullptr);
   std::vector<size_t> blen(count, 0);
@@ -122,17 +131,43 @@ int zt_zip_compress(const uint8_t *const *in, const size_t *n, const zt_zip_file
     ZT_TRY(zt_crc32_batch(pi.data(), pn.data(), stored.size(), c2.data()));
     for (size_t k = 0; k < stored.size(); ++k) crc[stored[k]] = c2[k];
   }
+  // encryption: E(header12 | body) of every protected entry, one batch
+  // (src/Zip.ts:152-187)
+  std::vector<std::vector<uint8_t>> enc(count);
+  if (crypt) {
+    std::vector<zc::Src> src;
+    std::vector<zc::Keys> keys;
+    std::vector<uint8_t *> dst;
+    std::vector<uint8_t> heads;
+    size_t ne = 0;
+    for (size_t i = 0; i < count; ++i) ne += crypt[i].password != nullptr;
+    heads.resize(12 * ne);
+    for (size_t i = 0, k = 0; i < count; ++i) {
+      if (!crypt[i].password) continue;
+      const bool d8 = files[i].method == 8;
+      const size_t bl = d8 ? blen[i] - 18 : n[i];
+      uint8_t *h = heads.data() + 12 * k++;
+      zc::crypt_header(crypt[i], crc[i], h);
+      enc[i].resize(zc::entry_data_len(true, bl));
+      src.push_back(zc::Src{h, 12, d8 ? body[i] + 10 : in[i], bl});
+      keys.push_back(zc::create_key(crypt[i].password, crypt[i].password_len));
+      dst.push_back(enc[i].data());
+    }
+    if (ne) ZT_TRY(zc::crypt_items(true, src.data(), keys.data(), ne, dst.data()));
+  }
   // layout: src/Zip.ts:189-372
   std::vector<uint8_t> lo, cd;
   for (size_t i = 0; i < count; ++i) {
     const zt_zip_file &f = files[i];
-    const uint8_t *data = f.method == 8 ? body[i] + 10 : in[i];
-    const size_t dlen = f.method == 8 ? blen[i] - 18 : n[i];
+    const bool encrypted = crypt && crypt[i].password;
+    const uint8_t *data = encrypted ? enc[i].data() : f.method == 8 ? body[i] + 10 : in[i];
+    const size_t dlen = encrypted ? enc[i].size() : f.method == 8 ? blen[i] - 18 : n[i];
+    const uint32_t flags = encrypted ? 1 : 0;  // ZipFlags.ENCRYPT (src/Zip.ts:247-249)
     const uint32_t offset = (uint32_t)lo.size();
     // local file header
     lo.insert(lo.end(), {0x50, 0x4b, 0x03, 0x04});
     put16(lo, 20);                 // version needed
-    put16(lo, 0);                  // flags
+    put16(lo, flags);
     put16(lo, (uint32_t)f.method);
     lo.insert(lo.end(), f.mtime, f.mtime + 4);
     put32(lo, crc[i]);
@@ -147,7 +182,7 @@ int zt_zip_compress(const uint8_t *const *in, const size_t *n, const zt_zip_file
     cd.push_back(20);              // version made by
     cd.push_back((uint8_t)f.os);
     put16(cd, 20);
-    put16(cd, 0);
+    put16(cd, flags);
     put16(cd, (uint32_t)f.method);
     cd.insert(cd.end(), f.mtime, f.mtime + 4);
     put32(cd, crc[i]);
@@ -181,8 +216,8 @@ int zt_zip_compress(const uint8_t *const *in, const size_t *n, const zt_zip_file
   return ZT_OK;
 }
 
-int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out_len, zt_unzip_entry **entries,
-             size_t *count) {
+int unzip_impl(const uint8_t *in, size_t n, int verify, const uint8_t *password, size_t password_len, uint8_t **out,
+               size_t *out_len, zt_unzip_entry **entries, size_t *count) {
   if (!out || !out_len || !entries || !count) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
   *out = nullptr;
@@ -237,7 +272,7 @@ int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out
   // local headers: src/Unzip.ts:28-62, 248-291
   std::vector<size_t> doff(total, 0), dlen(total, 0);
   std::vector<char> open_end(total, 0);
-  std::vector<size_t> defl;
+  std::vector<size_t> defl, encd;
   for (uint32_t i = 0; i < total; ++i) {
     zt_unzip_entry &e = ent[i];
     BS l{in, n, e.local_offset};
@@ -259,8 +294,22 @@ int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out
     e.local_crc32 = lcrc;
     e.local_method = method;
     if (flags & 1) {
-      e.status = ZT_E_ZIP_ENCRYPTED;
-      snprintf(e.message, sizeof e.message, "encrypted: please set password");
+      if (!password) {
+        e.status = ZT_E_ZIP_ENCRYPTED;
+        snprintf(e.message, sizeof e.message, "encrypted: please set password");
+        continue;
+      }
+      // the cipher stream: 12 header bytes, then the data (src/Unzip.ts:269-281)
+      size_t span;
+      if (!zc::encrypted_span(n, l.p, csize, e.compressed_size, &span)) {
+        e.status = ZT_E_ZIP_FORMAT;
+        snprintf(e.message, sizeof e.message, "invalid encryption header size");
+        continue;
+      }
+      encd.push_back(i);
+      doff[i] = l.p + 12;
+      dlen[i] = span - 12;
+      if (method == 8) defl.push_back(i);
       continue;
     }
     doff[i] = l.p;
@@ -281,13 +330,40 @@ int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out
       for (uint8_t *p : v) zt_free(p);
     }
   } freer{o};
-  if (!defl.empty()) {
-    DeviceCtx *dc;
+  DeviceCtx *dc = nullptr;
+  void *d_in = nullptr;
+  std::unique_lock<std::recursive_mutex> ctx_lock;
+  if (!defl.empty() || !encd.empty()) {
     ZT_TRY(get_ctx(&dc));
-    std::lock_guard<std::recursive_mutex> ctx_lock(dc->mu);
-    void *d_in;
+    ctx_lock = std::unique_lock<std::recursive_mutex>(dc->mu);
     ZT_TRY(scratch(dc, 19, n + 64, &d_in));
     ZT_TRY(upload(dc, d_in, in, n, dc->stream));
+  }
+  // protected entries: decrypted in place in the device copy, one lane each
+  std::vector<char> is_enc(total, 0);
+  if (!encd.empty()) {
+    const zc::Keys key = zc::create_key(password, password_len);
+    std::vector<zc::Stream> st(encd.size());
+    for (size_t k = 0; k < encd.size(); ++k) {
+      const size_t i = encd[k];
+      is_enc[i] = 1;
+      st[k] = zc::Stream{};
+      st[k].off = doff[i] - 12;
+      st[k].len = dlen[i] + 12;
+      memcpy(st[k].key, key.k, sizeof key.k);
+    }
+    void *d_st = nullptr;
+    ZT_HIP(hipMalloc(&d_st, st.size() * sizeof(zc::Stream)));
+    hipError_t he = hipMemcpyAsync(d_st, st.data(), st.size() * sizeof(zc::Stream), hipMemcpyHostToDevice, dc->stream);
+    int rc = he == hipSuccess ? zc::decrypt_dev(static_cast<uint8_t *>(d_in), static_cast<const zc::Stream *>(d_st),
+                                                st.size(), dc->stream)
+                              : ZT_OK;
+    if (he == hipSuccess && !rc) he = hipStreamSynchronize(dc->stream);
+    (void)hipFree(d_st);
+    if (rc) return rc;
+    ZT_HIP(he);
+  }
+  if (!defl.empty()) {
     const size_t m = defl.size();
     // (a member with a known compressed size reads at most 64 KiB past it:
     // a valid stream ends inside, and only a corrupt one would read on into
@@ -371,7 +447,10 @@ int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out
     const size_t a = std::min(doff[i], n), len = std::min(dlen[i], n - a);
     o[i] = (uint8_t *)malloc(len ? len : 1);
     if (!o[i]) return set_error(ZT_E_NOMEM, "host allocation failed");
-    if (len) memcpy(o[i], in + a, len);
+    if (len && is_enc[i])  // (the plaintext exists only in the device copy)
+      ZT_TRY(download(dc, o[i], static_cast<const uint8_t *>(d_in) + a, len, dc->stream));
+    else if (len)
+      memcpy(o[i], in + a, len);
     ol[i] = len;
   }
   // the output: every entry's data, concatenated
@@ -420,6 +499,32 @@ int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out
   for (uint32_t i = 0; i < total; ++i)
     if (ent[i].status) return set_error(ent[i].status, ent[i].message);
   return ZT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zt_zip_compress(const uint8_t *const *in, const size_t *n, const zt_zip_file *files, size_t count,
+                    const uint8_t *comment, size_t comment_len, uint8_t **out, size_t *out_len) {
+  return zip_compress_impl(in, n, files, nullptr, count, comment, comment_len, out, out_len);
+}
+
+int zt_zip_compress_pw(const uint8_t *const *in, const size_t *n, const zt_zip_file *files,
+                       const zt_zip_crypt *crypt, size_t count, const uint8_t *comment, size_t comment_len,
+                       uint8_t **out, size_t *out_len) {
+  return zip_compress_impl(in, n, files, crypt, count, comment, comment_len, out, out_len);
+}
+
+int zt_unzip(const uint8_t *in, size_t n, int verify, uint8_t **out, size_t *out_len, zt_unzip_entry **entries,
+             size_t *count) {
+  return unzip_impl(in, n, verify, nullptr, 0, out, out_len, entries, count);
+}
+
+int zt_unzip_pw(const uint8_t *in, size_t n, int verify, const uint8_t *password, size_t password_len,
+                uint8_t **out, size_t *out_len, zt_unzip_entry **entries, size_t *count) {
+  if (password_len && !password) return set_error(ZT_E_ARG, "null password");
+  return unzip_impl(in, n, verify, password, password_len, out, out_len, entries, count);
 }
 
 }  // extern "C"

@@ -4,8 +4,12 @@
 // directory and local headers are parsed with the reference's checks and
 // messages and every DEFLATE member is inflated in one GPU batch; each
 // getFileData(i) then returns entry i or throws its error as the reference
-// would.  ZipCrypto is not supported.
-import native, { refError } from './native.js';
+// would.  The password option, setPassword and the per-call {password} of
+// getFileData / decompress (src/Unzip.ts:263-282) decrypt ZipCrypto entries on
+// the GPU (zt_unzip_pw); the decoded archive is cached per password, and unlike
+// the reference the input is never written.
+import native, { dflt, refError } from './native.js';
+import { passwordBytes } from './Zip.js';
 
 function readString(input, off, len) {
     let s = '';
@@ -19,25 +23,28 @@ export class Unzip {
         this.ip = 0;
         this.EOCD = null;
         this.verify = !!opts.verify;
-        if (opts.password) this.password = opts.password;
-        this.decoded = null;
+        if (opts.password) this.password = passwordBytes(opts.password);
+        this.decoded = new Map();  // password (hex, '' for none) -> decoded archive
     }
 
-    decode() {
-        if (this.decoded) return this.decoded;
+    // `password` falsy: none, as the reference's `if (!password) throw`
+    decode(password) {
+        const pw = password ? passwordBytes(password) : null;
+        const key = pw ? 'p' + Buffer.from(pw).toString('hex') : '';
+        if (this.decoded.has(key)) return this.decoded.get(key);
         let r;
         try {
-            r = native.unzip(this.input, this.verify);
+            r = native.unzip(this.input, this.verify, pw);
         } catch (e) {
             throw refError(e);
         }
-        this.decoded = r;
+        this.decoded.set(key, r);
         return r;
     }
 
     parseFileHeader() {
         if (this.fileHeaderList) return;
-        const r = this.decode();
+        const r = this.decode(this.password);
         const list = [];
         const table = {};
         r.entries.forEach((e, i) => {
@@ -53,12 +60,14 @@ export class Unzip {
         this.filenameToIndex = table;
     }
 
-    getFileData(index) {
+    getFileData(index, opts = {}) {
         this.parseFileHeader();
-        const e = this.fileHeaderList[index];
-        if (e === undefined) throw new Error('wrong index');
+        if (this.fileHeaderList[index] === undefined) throw new Error('wrong index');
+        // src/Unzip.ts:265: the call's password, else the archive's
+        const r = this.decode(dflt(opts.password, this.password));
+        const e = r.entries[index];
         if (e.status !== 0) throw new Error(e.message);
-        return this.decoded.output.subarray(e.dataOff, e.dataOff + e.dataLen);
+        return r.output.subarray(e.dataOff, e.dataOff + e.dataLen);
     }
 
     getFilenames() {
@@ -66,14 +75,14 @@ export class Unzip {
         return this.fileHeaderList.map((e) => e.filename);
     }
 
-    decompress(filename) {
+    decompress(filename, opts = {}) {
         this.parseFileHeader();
         const index = this.filenameToIndex[filename];
         if (index === undefined) throw new Error(filename + ' not found');
-        return this.getFileData(index);
+        return this.getFileData(index, opts);
     }
 
     setPassword(password) {
-        this.password = password;
+        this.password = passwordBytes(password);
     }
 }

@@ -3,7 +3,13 @@
 // The archive is built by libzt (zt_zip_compress): every DEFLATE member of the
 // archive is compressed in one GPU batch pipeline and every CRC-32 comes from
 // the batched GPU checksum kernel; the layout is the reference's, byte for
-// byte.  ZipCrypto is not supported (a password throws).
+// byte.  Passwords (setPassword, addFile's password option) encrypt with
+// ZipCrypto on the GPU (zt_zip_compress_pw, src/Zip.ts:152-187): by default
+// with the encryption header exactly as the reference writes it
+// (cryptHeader: 'reference'); the extension cryptHeader: 'pkware' writes the
+// header other tools check (the CRC's high bytes) after 10 random bytes, or
+// after the option cryptLead.
+import crypto from 'crypto';
 import native, { dflt, refError } from './native.js';
 import { CompressionType } from './Constants.js';
 
@@ -29,6 +35,12 @@ export function dosTime(date) {
         ((date.getMonth() + 1 & 0x7) << 5) | (date.getDate()),
         ((date.getFullYear() - 1980 & 0x7f) << 1) | (date.getMonth() + 1 >> 3),
     ]);
+}
+
+// a password as bytes (ZipCrypto.createKey, src/ZipCrypto.ts:35-36)
+export function passwordBytes(password) {
+    if (typeof password === 'string') return stringToByteArray(password);
+    return password instanceof Uint8Array ? password : new Uint8Array(password);
 }
 
 export class Zip {
@@ -59,8 +71,20 @@ export class Zip {
 
     compress() {
         const files = this.files.map((f) => {
-            if (f.option.password !== undefined || this.password !== null) {
-                throw new Error('zlib.ts_amd: ZipCrypto is not supported');
+            // src/Zip.ts:153-155: the file's own password, else the archive's
+            let password = null, cryptHeader = 0, cryptLead = null;
+            if ((f.option.password !== undefined && f.option.password !== null) ||
+                (this.password !== undefined && this.password !== null)) {
+                password = passwordBytes(dflt(f.option.password, this.password));
+                const mode = dflt(f.option.cryptHeader, 'reference');
+                if (mode !== 'reference' && mode !== 'pkware') throw new Error('invalid cryptHeader: ' + mode);
+                cryptHeader = mode === 'pkware' ? 1 : 0;
+                if (f.option.cryptLead !== undefined && f.option.cryptLead !== null) {
+                    cryptLead = passwordBytes(f.option.cryptLead);
+                    if (cryptLead.length !== 10) throw new Error('cryptLead must be 10 bytes');
+                } else if (cryptHeader === 1) {
+                    cryptLead = new Uint8Array(crypto.randomBytes(10));
+                }
             }
             const date = f.option.date !== undefined && f.option.date !== null ? f.option.date : new Date();
             f.option.mtime = dosTime(date);
@@ -75,6 +99,9 @@ export class Zip {
                 compressionType: dflt(d.compressionType, CompressionType.DYNAMIC),
                 lazy: dflt(d.lazy, 0),
                 level: dflt(d.level, 6),
+                password,
+                cryptHeader,
+                cryptLead,
             };
         });
         try {

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/zt.h"
+#include "../../include/zt_zipcrypto.h"
 
 namespace {
 
@@ -359,7 +360,9 @@ napi_value prop(napi_env env, napi_value obj, const char *k) {
 }
 
 // zipCompress(files: [{data, name, comment (or null), method, os, mtime (4 bytes),
-//             compressionType, lazy, level}], comment: Uint8Array) -> Uint8Array
+//             compressionType, lazy, level, password (Uint8Array or null),
+//             cryptHeader (0 reference | 1 PKWARE), cryptLead (10 bytes or null)}],
+//             comment: Uint8Array) -> Uint8Array
 napi_value zip_compress(napi_env env, napi_callback_info info) {
   napi_value a[2];
   args(env, info, a, 2);
@@ -368,6 +371,8 @@ napi_value zip_compress(napi_env env, napi_callback_info info) {
   std::vector<const uint8_t *> in(cnt);
   std::vector<size_t> n(cnt);
   std::vector<zt_zip_file> f(cnt);
+  std::vector<zt_zip_crypt> cr(cnt);
+  bool any_pw = false;
   for (uint32_t i = 0; i < cnt; ++i) {
     napi_value e;
     napi_get_element(env, a[0], i, &e);
@@ -385,6 +390,21 @@ napi_value zip_compress(napi_env env, napi_callback_info info) {
     f[i].deflate.compression_type = (int)get_i64(env, prop(env, e, "compressionType"), 2);
     f[i].deflate.lazy = (int)get_i64(env, prop(env, e, "lazy"), 0);
     f[i].deflate.level = (int)get_i64(env, prop(env, e, "level"), -1);
+    memset(&cr[i], 0, sizeof cr[i]);
+    bool has_pw = false, has_lead = false;
+    static const uint8_t kEmpty = 0;
+    if (!opt_u8(env, prop(env, e, "password"), &cr[i].password, &cr[i].password_len, &has_pw)) return nullptr;
+    if (has_pw) {
+      any_pw = true;
+      if (!cr[i].password) cr[i].password = &kEmpty;  // (an empty password is still one)
+      cr[i].header_mode = (int)get_i64(env, prop(env, e, "cryptHeader"), 0);
+      const uint8_t *ld = nullptr;
+      size_t ll = 0;
+      if (!opt_u8(env, prop(env, e, "cryptLead"), &ld, &ll, &has_lead)) return nullptr;
+      for (size_t k = 0; k < 10 && k < ll; ++k) cr[i].lead[k] = ld[k];
+    } else {
+      cr[i].password = nullptr;
+    }
   }
   const uint8_t *cm = nullptr;
   size_t cl = 0;
@@ -392,16 +412,17 @@ napi_value zip_compress(napi_env env, napi_callback_info info) {
   if (!opt_u8(env, a[1], &cm, &cl, &has)) return nullptr;
   uint8_t *out = nullptr;
   size_t olen = 0;
-  const int rc = zt_zip_compress(in.data(), n.data(), f.data(), cnt, cm, cl, &out, &olen);
+  const int rc = any_pw ? zt_zip_compress_pw(in.data(), n.data(), f.data(), cr.data(), cnt, cm, cl, &out, &olen)
+                        : zt_zip_compress(in.data(), n.data(), f.data(), cnt, cm, cl, &out, &olen);
   if (rc) return throw_zt(env, rc);
   return new_u8(env, out, olen);
 }
 
-// unzip(input, verify) -> {output, entries: [{nameOff, nameLen, ..., status, message}]}
+// unzip(input, verify, password (Uint8Array or null)) -> {output, entries: [{nameOff, nameLen, ..., status, message}]}
 // (archive-level errors throw; an entry's error is in its status / message)
 napi_value unzip(napi_env env, napi_callback_info info) {
-  napi_value a[2];
-  args(env, info, a, 2);
+  napi_value a[3];
+  args(env, info, a, 3);
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -409,10 +430,17 @@ napi_value unzip(napi_env env, napi_callback_info info) {
   napi_valuetype t;
   napi_typeof(env, a[1], &t);
   if (t == napi_boolean) napi_get_value_bool(env, a[1], &verify);
+  const uint8_t *pw = nullptr;
+  size_t pwn = 0;
+  bool has_pw = false;
+  static const uint8_t kEmpty = 0;
+  if (!opt_u8(env, a[2], &pw, &pwn, &has_pw)) return nullptr;
+  if (has_pw && !pw) pw = &kEmpty;
   uint8_t *out = nullptr;
   size_t olen = 0, cnt = 0;
   zt_unzip_entry *ent = nullptr;
-  const int rc = zt_unzip(p, n, verify ? 1 : 0, &out, &olen, &ent, &cnt);
+  const int rc = has_pw ? zt_unzip_pw(p, n, verify ? 1 : 0, pw, pwn, &out, &olen, &ent, &cnt)
+                        : zt_unzip(p, n, verify ? 1 : 0, &out, &olen, &ent, &cnt);
   if (rc && !ent) return throw_zt(env, rc);
   napi_value obj, arr;
   napi_create_object(env, &obj);

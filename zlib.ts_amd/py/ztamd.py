@@ -17,7 +17,7 @@ ERRORS = {
     -15: "ZT_E_INVALID_DISTANCE", -16: "ZT_E_INVALID_SYMBOL", -17: "ZT_E_BAD_TREE",
     -30: "ZT_E_GZIP_SIGNATURE", -31: "ZT_E_GZIP_METHOD", -32: "ZT_E_GZIP_HCRC", -33: "ZT_E_GZIP_CRC32",
     -34: "ZT_E_GZIP_ISIZE", -40: "ZT_E_ZLIB_METHOD", -41: "ZT_E_ZLIB_FCHECK", -42: "ZT_E_ZLIB_FDICT",
-    -43: "ZT_E_ZLIB_ADLER", -100: "ZT_E_NO_DEVICE",
+    -43: "ZT_E_ZLIB_ADLER", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED", -100: "ZT_E_NO_DEVICE",
     -101: "ZT_E_HIP", -102: "ZT_E_NOMEM", -103: "ZT_E_ARG", -104: "ZT_E_INTERNAL",
 }
 
@@ -46,6 +46,11 @@ class ZipFile(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("name_len", ctypes.c_size_t), ("comment", ctypes.c_char_p),
                 ("comment_len", ctypes.c_size_t), ("method", ctypes.c_int), ("os", ctypes.c_int),
                 ("mtime", ctypes.c_uint8 * 4), ("deflate", DeflateOpts)]
+
+
+class ZipCrypt(ctypes.Structure):
+    _fields_ = [("password", ctypes.c_char_p), ("password_len", ctypes.c_size_t), ("header_mode", ctypes.c_int),
+                ("lead", ctypes.c_uint8 * 10)]
 
 
 class UnzipEntry(ctypes.Structure):
@@ -132,6 +137,14 @@ def _load():
         "zt_timing_read": ([P(KernelTimes)], ctypes.c_int),
         "zt_scratch_bytes": ([P(sz), P(sz)], ctypes.c_int),
         "zt_release_scratch": ([], ctypes.c_int),
+        # include/zt_zipcrypto.h
+        "zt_zipcrypto_encrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
+        "zt_zipcrypto_decrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
+        "zt_zipcrypto_tile_bytes": ([], sz),
+        "zt_zipcrypto_chunk_bytes": ([], sz),
+        "zt_zipcrypto_last_kernel_ms": ([P(ctypes.c_double)], ctypes.c_int),
+        "zt_zip_compress_pw": ([P(vp), P(sz), P(ZipFile), P(ZipCrypt), sz, vp, sz, u8pp, P(sz)], ctypes.c_int),
+        "zt_unzip_pw": ([vp, sz, ctypes.c_int, vp, sz, u8pp, P(sz), P(P(UnzipEntry)), P(sz)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -155,6 +168,12 @@ SYMBOLS = [
     "zt_deflate_bound", "zt_deflate_dev", "zt_inflate_plan_create", "zt_inflate_plan_destroy", "zt_inflate_dev",
     "zt_synth_dev", "zt_synth_dev_at", "zt_timing_enable", "zt_timing_read", "zt_scratch_bytes",
     "zt_release_scratch",
+]
+
+# every symbol include/zt_zipcrypto.h declares (checked by tests/test_zipcrypto_ref.py)
+ZIPCRYPTO_SYMBOLS = [
+    "zt_zipcrypto_encrypt_batch", "zt_zipcrypto_decrypt_batch", "zt_zipcrypto_tile_bytes",
+    "zt_zipcrypto_chunk_bytes", "zt_zipcrypto_last_kernel_ms", "zt_zip_compress_pw", "zt_unzip_pw",
 ]
 
 
@@ -411,9 +430,23 @@ def dos_mtime(year, month, day, hour, minute, second):
                   ((month & 7) << 5) | day, (((year - 1980) & 0x7F) << 1) | (month >> 3)])
 
 
-def zip_compress(files, comment=b""):
+CRYPT_HEADERS = {"reference": 0, "pkware": 1}
+
+
+def _pw_bytes(pw):
+    """A password as bytes (a str as stringToByteArray does: charCode & 0xFF)."""
+    return bytes(ord(ch) & 0xFF for ch in pw) if isinstance(pw, str) else bytes(pw)
+
+
+def zip_compress(files, comment=b"", pw_call=False):
     """Zip.addFile(...) for each dict of `files` (data, name, comment, method,
-    os, mtime = 4 DOS bytes, compression_type, lazy) then Zip.compress()."""
+    os, mtime = 4 DOS bytes, compression_type, lazy) then Zip.compress().
+    A file with `password` (bytes or str) is encrypted with ZipCrypto:
+    `crypt_header` 'reference' (default: header bytes as src/Zip.ts writes
+    them) or 'pkware' (as other tools check them), `crypt_lead` = the 10
+    leading header bytes (default zeros; the library draws no randomness).
+    pw_call: go through zt_zip_compress_pw even when no file has a password
+    (crypt = NULL)."""
     k = len(files)
     datas = [bytes(f["data"]) for f in files]
     bs, ptrs, lens = _batch_ptrs(datas)
@@ -432,20 +465,82 @@ def zip_compress(files, comment=b""):
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     cb = bytes(comment)
-    _check(lib.zt_zip_compress(ptrs, lens, arr, k, cb, len(cb), ctypes.byref(out), ctypes.byref(olen)))
+    if any(f.get("password") is not None for f in files):
+        cr = (ZipCrypt * k)()
+        for i, f in enumerate(files):
+            if f.get("password") is None:
+                continue
+            pw = _pw_bytes(f["password"])
+            keep.append(pw)
+            cr[i].password, cr[i].password_len = pw, len(pw)
+            cr[i].header_mode = CRYPT_HEADERS[f.get("crypt_header", "reference")]
+            lead = bytes(f.get("crypt_lead", bytes(10)))
+            if len(lead) != 10:
+                raise ValueError("crypt_lead must be 10 bytes")
+            cr[i].lead = (ctypes.c_uint8 * 10)(*lead)
+        _check(lib.zt_zip_compress_pw(ptrs, lens, arr, cr, k, cb, len(cb), ctypes.byref(out), ctypes.byref(olen)))
+    elif pw_call:
+        _check(lib.zt_zip_compress_pw(ptrs, lens, arr, None, k, cb, len(cb), ctypes.byref(out), ctypes.byref(olen)))
+    else:
+        _check(lib.zt_zip_compress(ptrs, lens, arr, k, cb, len(cb), ctypes.byref(out), ctypes.byref(olen)))
     return _take(out, olen)
 
 
-def unzip(archive, verify=False):
+def _zipcrypto_batch(fn, items, passwords):
+    bs, ptrs, lens = _batch_ptrs(items)
+    k = len(bs)
+    if not isinstance(passwords, (list, tuple)):
+        passwords = [passwords] * k
+    pws, pptrs, plens = _batch_ptrs([_pw_bytes(p) for p in passwords])
+    if len(pws) != k:
+        raise ValueError("one password per item")
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    _check(fn(ptrs, lens, k, pptrs, plens, outs))
+    return _batch_take(k, outs, lens)
+
+
+def zipcrypto_encrypt(items, passwords):
+    """Raw ZipCrypto streams (no container) of `items` under `passwords` (one
+    for all, or one per item)."""
+    return _zipcrypto_batch(lib.zt_zipcrypto_encrypt_batch, items, passwords)
+
+
+def zipcrypto_decrypt(items, passwords):
+    return _zipcrypto_batch(lib.zt_zipcrypto_decrypt_batch, items, passwords)
+
+
+def zipcrypto_geometry():
+    """(tile bytes T, chunk bytes C) of the encrypt kernels."""
+    return lib.zt_zipcrypto_tile_bytes(), lib.zt_zipcrypto_chunk_bytes()
+
+
+def zipcrypto_last_kernel_ms():
+    ms = ctypes.c_double()
+    _check(lib.zt_zipcrypto_last_kernel_ms(ctypes.byref(ms)))
+    return ms.value
+
+
+def unzip(archive, verify=False, password=None, pw_call=False):
     """Unzip every entry.  Returns (first error or None, [entry dicts with
-    name, comment, data (or None), status, message and the header fields])."""
+    name, comment, data (or None), status, message and the header fields]).
+    `password` (bytes or str) decrypts the archive's ZipCrypto entries
+    (pw_call: zt_unzip_pw even without one, password = NULL)."""
     b, n = _cbuf(archive)
     archive = bytes(archive)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     ents = ctypes.POINTER(UnzipEntry)()
     cnt = ctypes.c_size_t()
-    rc = lib.zt_unzip(b, n, int(verify), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(ents), ctypes.byref(cnt))
+    if password is None and pw_call:
+        rc = lib.zt_unzip_pw(b, n, int(verify), None, 0, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(ents),
+                             ctypes.byref(cnt))
+    elif password is None:
+        rc = lib.zt_unzip(b, n, int(verify), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(ents),
+                          ctypes.byref(cnt))
+    else:
+        pw, pn = _cbuf(_pw_bytes(password))
+        rc = lib.zt_unzip_pw(b, n, int(verify), pw, pn, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(ents),
+                             ctypes.byref(cnt))
     if rc != ZT_OK and not ents:
         return ZtError(rc, lib.zt_last_error_message().decode(errors="replace")), []
     data = ctypes.string_at(out, olen.value) if out else b""
