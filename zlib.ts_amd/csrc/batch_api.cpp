@@ -110,7 +110,7 @@ constexpr uint64_t kGroupMin = 256ull << 20;
 
 int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size_t> &work,
                   const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, uint64_t padded, int ct, int lv,
-                  const Framing &fr, uint8_t **out, size_t *out_len, StageTimes &tm) {
+                  const Framing &fr, uint8_t **out, size_t *out_len, StageTimes &tm, const DictHist *dh) {
   const size_t m = work.size();
   const bool sums = fr.kind != Framing::RAW;
   // groups [gk[g], gk[g + 1]) of items
@@ -256,7 +256,7 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size
                               c->aux));
       }
       ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), ct, lv,
-                                   (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, c->stream));
+                                   (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, c->stream, dh));
       if (sums) ZT_HIP(hipStreamSynchronize(c->aux));
       return ZT_OK;
     };
@@ -277,7 +277,7 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size
 
 // one device's share: items `ids` of the batch
 int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids, int ct,
-                    int lv, const Framing &fr, uint8_t **out, size_t *out_len, std::string *err) {
+                    int lv, const Framing &fr, uint8_t **out, size_t *out_len, std::string *err, const HostDict &hd) {
   auto fail = [&](int rc) {
     *err = zt_last_error_message();
     return rc;
@@ -300,6 +300,22 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     }
   }
   if (work.empty()) return ZT_OK;
+  // preset dictionary: one copy per device of the history the match kernel
+  // loads in front of every stream (dict_host.h: padding | usable tail)
+  DictHist dict_dev{nullptr, 0, 0};
+  const DictHist *dh = nullptr;
+  std::vector<uint8_t> dict_img;
+  if (hd.dict_len && ct != 0) {
+    const DictLayout L = dict_layout(hd.dict_len);
+    void *d_dict;
+    if (int rc = scratch(c, 29, L.hist, &d_dict)) return fail(rc);
+    dict_img.resize(L.hist);
+    dict_fill_history(L, hd.dict, dict_img.data());
+    ZT_HIP(hipMemcpyAsync(d_dict, dict_img.data(), L.hist, hipMemcpyHostToDevice, c->stream));
+    ZT_HIP(hipStreamSynchronize(c->stream));
+    dict_dev = DictHist{static_cast<const uint8_t *>(d_dict), L.hist, L.floor};
+    dh = &dict_dev;
+  }
   const size_t m = work.size();
   std::vector<uint64_t> off(m), len(m);
   uint64_t padded = 0, in_bytes = 0;
@@ -323,7 +339,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     }
   } report{tm, t_start, dev};
   if (ct != 0 && padded >= kGroupMin && m >= 2) {
-    const int rc = batch_grouped(c, in, work, off, len, padded, ct, lv, fr, out, out_len, tm);
+    const int rc = batch_grouped(c, in, work, off, len, padded, ct, lv, fr, out, out_len, tm, dh);
     return rc ? fail(rc) : ZT_OK;
   }
   void *d_in, *h_stage;
@@ -387,7 +403,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     const size_t ss = deflate_batch_scratch_bytes(c, padded);
     if (int rc = scratch(c, 3, ss, &d_scr)) return fail(rc);
     if (int rc = deflate_batch_dev_run(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv,
-                                       (uint8_t *)d_out, oo.data(), d_scr, ss, c->stream))
+                                       (uint8_t *)d_out, oo.data(), d_scr, ss, c->stream, dh))
       return fail(rc);
     // The members are framed on the device (prefix | stream | trailer, at
     // their slab offsets) and come back with one copy -- straight into the
@@ -464,7 +480,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
 
 // split over the batch devices (LPT) and run every share on its own thread
 int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, int lv, const Framing &fr,
-              uint8_t **out, size_t *out_len, int *status) {
+              uint8_t **out, size_t *out_len, int *status, const HostDict &hd = HostDict()) {
   for (size_t i = 0; i < count; ++i) {
     out[i] = nullptr;
     out_len[i] = 0;
@@ -492,7 +508,7 @@ int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, i
   std::vector<std::string> err(nd);
   const int caller_dev = current_device();
   if (nd == 1) {
-    rc[0] = batch_on_device(devs[0], in, n, share[0], ct, lv, fr, out, out_len, &err[0]);
+    rc[0] = batch_on_device(devs[0], in, n, share[0], ct, lv, fr, out, out_len, &err[0], hd);
     zt_set_device(caller_dev);
   } else {
     std::vector<std::thread> th;
@@ -505,7 +521,7 @@ int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, i
         // ZT_BATCH_COPY_THREADS overrides the total
         static const size_t total = getenv("ZT_BATCH_COPY_THREADS") ? (size_t)atoi(getenv("ZT_BATCH_COPY_THREADS")) : 32;
         set_copy_threads(std::max<size_t>(2, total / nd));
-        rc[d] = batch_on_device(devs[d], in, n, share[d], ct, lv, fr, out, out_len, &err[d]);
+        rc[d] = batch_on_device(devs[d], in, n, share[d], ct, lv, fr, out, out_len, &err[d], hd);
       });
     for (auto &t : th) t.join();
   }
@@ -540,6 +556,22 @@ int resolve_opts(const zt_deflate_opts *o, int *ct, int *lv) {
 }
 
 }  // namespace
+
+// zt_dict.h's batch deflate calls (dict_api.cpp): raw streams, or zlib members
+// whose header carries FDICT and the dictionary's Adler-32
+int deflate_batch_host(const uint8_t *const *in, const size_t *n, size_t count, const zt_deflate_opts *opts,
+                       const HostDict &hd, bool zlib, uint32_t dictid, uint8_t **out, size_t *out_len, int *status) {
+  int ct, lv;
+  ZT_TRY(resolve_opts(opts, &ct, &lv));
+  Framing fr{Framing::RAW, {}, 0};
+  if (zlib) {
+    uint8_t h6[6];
+    zlib_dict_header(0x78, (uint32_t)(opts ? opts->compression_type : 2), dictid, h6);
+    fr = Framing{Framing::ZLIB, std::vector<uint8_t>(h6, h6 + 6), 4};
+  }
+  return run_batch(in, n, count, ct, lv, fr, out, out_len, status, hd);
+}
+
 }  // namespace zt
 
 using namespace zt;

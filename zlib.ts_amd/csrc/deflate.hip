@@ -170,6 +170,21 @@ struct DeflateParams {
   BlockPlan *plans;     // nblocks
 };
 
+// Preset dictionary of a batch (second argument of classify_dict_kernel and
+// match_dict_kernel; launches without a dictionary run classify_kernel and
+// match_kernel, which take DeflateParams alone and hold no dictionary code).
+// The first workgroup of every stream loads `hist` bytes of history from
+// `dict` instead of from the bytes before the stream.  dict holds the usable
+// tail of the dictionary (its last DF_MAXDIST bytes at most) right-aligned in
+// hist = round_up(tail, DF_SUB) bytes; the floor = hist - tail bytes in front
+// are padding: rel positions below the floor are never linked into the
+// chains, never probed and never a match source.
+struct DictView {
+  const uint8_t *dict;
+  uint32_t hist;
+  uint32_t floor;
+};
+
 // per-block coding decisions (block_kernel -> encode_kernel)
 struct BlockPlan {
   uint32_t lit_code[288];  // len << 16 | bit-reversed code
@@ -288,6 +303,23 @@ __device__ __forceinline__ uint32_t cl_gword(const uint8_t *g, int64_t off, uint
     if (off + k < (int64_t)end) v |= (uint32_t)a[k] << (8 * k);
   return v;
 }
+// 4 bytes at offset wo of the window [dictionary tail dt[0 .. dlen) | stream
+// bytes from g + lo on] of a stream's first block (bytes past `end` read as 0)
+__device__ __forceinline__ uint32_t cl_dword(const uint8_t *dt, uint32_t dlen, const uint8_t *g, uint64_t lo,
+                                             uint64_t end, uint32_t wo) {
+  if (wo >= dlen) return cl_gword(g, (int64_t)(lo + (wo - dlen)), end);
+  uint32_t v = 0;
+  for (uint32_t k = 0; k < 4; ++k) {
+    const uint32_t o = wo + k;
+    uint32_t b = 0;
+    if (o < dlen)
+      b = dt[o];
+    else if (lo + (o - dlen) < end)
+      b = g[lo + (o - dlen)];
+    v |= b << (8 * k);
+  }
+  return v;
+}
 // 13-bit bucket and 16-bit fingerprint of an 8-byte key
 __device__ __forceinline__ uint32_t cl_hash(uint32_t a, uint32_t b) {
   uint32_t h = a * 0x9E3779B1u ^ b * 0x85EBCA77u;
@@ -295,7 +327,8 @@ __device__ __forceinline__ uint32_t cl_hash(uint32_t a, uint32_t b) {
   return h * 0x2C1B3C6Du;
 }
 
-__global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) {
+template <bool DICT>
+__device__ __forceinline__ void classify_body(const DeflateParams P, const DictView D) {
   __shared__ ClassifyShared sh;
   ClassifyShared *s = &sh;
   const uint32_t t = threadIdx.x, blk = blockIdx.x;
@@ -347,14 +380,20 @@ __global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) {
   int64_t h0 = (int64_t)lo - DF_HIST;
   const int64_t floor_ = halo_hist ? -(int64_t)(P.halo < (uint64_t)DF_HIST ? P.halo : (uint64_t)DF_HIST) : (int64_t)w_lo;
   if (h0 < floor_) h0 = floor_;
-  const uint32_t wlen = (uint32_t)((int64_t)lo + blen - h0);
+  // a stream's first block counts its preset dictionary as history: the
+  // window is the dictionary's usable tail, then the block
+  const bool dfirst = DICT && lo == f_lo;
+  const uint32_t dlen = dfirst ? D.hist - D.floor : 0u;
+  const uint8_t *dtail = dfirst ? D.dict + D.floor : nullptr;
+  const uint32_t wlen = (uint32_t)((int64_t)lo + blen - h0) + dlen;
   for (uint32_t i = t; i < CL_TABLE; i += 256) s->table[i] = CL_EMPTY;
   s->hist[t] = 0;  // (stage A's reads of it are behind the barrier above; B2 counts the whole block)
   // B1. inserts: every 16th position of the window (at most 15 per thread,
   // every load issued before the first is used); 8-byte loads when the
   // stream is 16-byte aligned and the window's reads stay inside it
   constexpr int NI = (DF_HIST + DF_BLOCK) / (16 * 256);
-  const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0 && (h0 & 15) == 0 && lo + DF_BLOCK + 8 <= n;
+  const bool vecb = (reinterpret_cast<uintptr_t>(g) & 15) == 0 && (h0 & 15) == 0 && lo + DF_BLOCK + 8 <= n;
+  const bool vec = vecb && !dfirst;  // (the inserts; the queries below read the block alone: vecb)
   typedef unsigned int cl_u32x2 __attribute__((ext_vector_type(2)));
   typedef unsigned int cl_u32x4 __attribute__((ext_vector_type(4)));
   {
@@ -374,7 +413,8 @@ __global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) {
       for (int i = 0; i < NI; ++i) {
         const int64_t a = a4 + 16 * (int64_t)(t + 256 * i);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) w[i][j] = cl_gword(g, a + 4 * j, n);
+        for (int j = 0; j < 3; ++j)
+          w[i][j] = dfirst ? cl_dword(dtail, dlen, g, lo, n, 16 * (t + 256 * i) + 4 * j) : cl_gword(g, a + 4 * j, n);
       }
     }
     __syncthreads();  // (the table's EMPTY stores before any insert)
@@ -384,17 +424,25 @@ __global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) {
       const uint32_t x0 = vec ? w[i][0] : __builtin_amdgcn_alignbyte(w[i][1], w[i][0], sh);
       const uint32_t x1 = vec ? w[i][1] : __builtin_amdgcn_alignbyte(w[i][2], w[i][1], sh);
       const uint32_t hh = cl_hash(x0, x1);
-      if (r + 8 <= wlen) s->table[hh >> 19] = (r << 16) | (hh & 0xFFFFu);
+      // (with a dictionary the oldest position of a bucket stays: a block
+      // that repeats dictionary bytes a multiple of 16 back inserts the same
+      // keys itself, and a query that finds only its own position is no hit)
+      if (r + 8 <= wlen) {
+        if (dfirst)
+          atomicMin(&s->table[hh >> 19], (r << 16) | (hh & 0xFFFFu));
+        else
+          s->table[hh >> 19] = (r << 16) | (hh & 0xFFFFu);
+      }
     }
   }
   __syncthreads();
   // B2. queries: thread t the 128 positions from lo + 128 t (block coordinates k)
-  const uint32_t b0 = (uint32_t)((int64_t)lo - h0);  // the block in window coordinates
+  const uint32_t b0 = (uint32_t)((int64_t)lo - h0) + dlen;  // the block in window coordinates
   uint32_t hits = 0;
   const uint32_t k0 = 128 * t;
   if (k0 < blen) {
     uint32_t w[36];
-    if (vec) {
+    if (vecb) {
       const cl_u32x4 *v4 = reinterpret_cast<const cl_u32x4 *>(g + lo + k0);
 #pragma unroll
       for (int j = 0; j < 9; ++j) {
@@ -459,6 +507,11 @@ __global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) {
     P.store[blk] = st ? 1 : 0;
     if (st) atomicAdd(P.nstore, 1u);
   }
+}
+
+__global__ __launch_bounds__(256) void classify_kernel(DeflateParams P) { classify_body<false>(P, DictView{}); }
+__global__ __launch_bounds__(256) void classify_dict_kernel(DeflateParams P, DictView D) {
+  classify_body<true>(P, D);
 }
 
 // ================================ 1. match_kernel ================================
@@ -937,17 +990,17 @@ __device__ __forceinline__ void walk_pair_step(Walk &a, Walk &b, const MatchShar
 // the near probes, then the newest earlier position with the same 4 bytes
 // (the 4-byte-key table; the chains' 8-byte keys miss the 4..7-byte matches
 // that make up much of source text)
-template <int K>
+template <int K, bool DICT>
 __device__ __forceinline__ uint32_t walk_finish(const Walk &w, const MatchShared *s, const DeflateParams &P,
                                                 const uint32_t (&win)[9], uint32_t near, uint32_t lim4, uint32_t d4,
-                                                uint32_t &carry_len, uint32_t &carry_dist) {
+                                                uint32_t floor, uint32_t &carry_len, uint32_t &carry_dist) {
   uint32_t best_len = w.best_len < w.cl ? w.cl : w.best_len, best_dist = w.best_dist;
   // a far 3-byte match (carried from the previous position) is dropped in
   // the end: it must not hide a near one
   if (best_len == 3 && best_dist > (uint32_t)P.too_far) best_len = 0;
   const bool short_ = best_len < (uint32_t)P.klen;
   if (near == 0 && w.max_len >= 3 && short_)
-    near_probe<K, 1>(win, w.cur, w.cur2, w.p, w.max_len, P.probe, best_len, best_dist);
+    near_probe<K, 1>(win, w.cur, w.cur2, DICT ? w.p - floor : w.p, w.max_len, P.probe, best_len, best_dist);
 #ifndef ZT_DF_NOP4
   // (positions from lim4 on have no 4-byte link: their keys would need bytes
   // past the segment's end)
@@ -973,9 +1026,14 @@ __device__ __forceinline__ uint32_t walk_finish(const Walk &w, const MatchShared
 }
 
 // longest match for positions [pb, pb + 4) of the sub-chunk [p0, p1) -> res_out[p - p0];
-// matches end at pml (>= p1)
+// matches end at pml (>= p1); floor: the first rel position that holds data
+// (0, or a preset dictionary's first byte: near probes stop there, the chains
+// and the 4-byte table never held a position below it).  DICT = false: the
+// floor is 0 at compile time
+template <bool DICT>
 __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32_t pb, uint32_t p0, uint32_t p1,
-                            uint32_t pml, uint32_t lim4, Key key, uint32_t *res_out, int mc, uint32_t &late) {
+                            uint32_t pml, uint32_t lim4, uint32_t floor, Key key, uint32_t *res_out, int mc,
+                            uint32_t &late) {
   if (pb >= p1) return;
   // bytes [pb - 16, pb + 20) (pb is a multiple of 4; before rel 0 the words
   // are never used: near distances stay <= p)
@@ -998,8 +1056,8 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
   walk_init(wa, s, P, pb, pml, win32<16>(w), win32<20>(w), win32<24>(w), win32<28>(w), 0, 0, l8.x & 0xFFFFu, mc);
   walk_init(wb, s, P, pb + 2, pml, win32<18>(w), win32<22>(w), win32<26>(w), win32<30>(w), 0, 0, l8.y & 0xFFFFu, mc);
   for (int step = 0; wa.active || wb.active; ++step) walk_pair_step(wa, wb, s, P, step);
-  out[0] = walk_finish<0>(wa, s, P, w, nr0, lim4, l4.x & 0xFFFFu, c0l, c0d);
-  out[2] = walk_finish<2>(wb, s, P, w, nr2, lim4, l4.y & 0xFFFFu, c2l, c2d);
+  out[0] = walk_finish<0, DICT>(wa, s, P, w, nr0, lim4, l4.x & 0xFFFFu, floor, c0l, c0d);
+  out[2] = walk_finish<2, DICT>(wb, s, P, w, nr2, lim4, l4.y & 0xFFFFu, floor, c2l, c2d);
 #ifdef ZT_DF_NOCARRY  // experiment: positions 1 and 3 start without the carried match
   c0l = c0d = c2l = c2d = 0;
 #endif
@@ -1007,8 +1065,8 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
   walk_init(wb, s, P, pb + 3, pml, win32<19>(w), win32<23>(w), win32<27>(w), win32<31>(w), c2l, c2d, l8.y >> 16, mc);
   for (int step = 0; wa.active || wb.active; ++step) walk_pair_step(wa, wb, s, P, step);
   late += wa.late + wb.late;
-  out[1] = walk_finish<1>(wa, s, P, w, nr1, lim4, l4.x >> 16, cl, cd);
-  out[3] = walk_finish<3>(wb, s, P, w, nr3, lim4, l4.y >> 16, cl, cd);
+  out[1] = walk_finish<1, DICT>(wa, s, P, w, nr1, lim4, l4.x >> 16, floor, cl, cd);
+  out[3] = walk_finish<3, DICT>(wb, s, P, w, nr3, lim4, l4.y >> 16, floor, cl, cd);
   // the positions' own bytes (res_pack)
   out[0] |= win32<16>(w) << 24;
   out[1] |= win32<17>(w) << 24;
@@ -1023,8 +1081,10 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
   }
 }
 
-__global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
-  __shared__ MatchShared s;
+// DICT: a batch whose streams have a preset dictionary (D); false: the code
+// of every launch without one, with no trace of the dictionary path
+template <bool DICT>
+__device__ __forceinline__ void match_body(const DeflateParams P, const DictView D, MatchShared &s) {
   const uint32_t t = threadIdx.x;
   // workgroups go to the 8 XCDs round robin, and every 8th super-chunk starts
   // a segment (no history: 18 % fewer positions): rotate each group of 8 so
@@ -1051,9 +1111,24 @@ __global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
                               : (b0 % P.restart) == 0 && (b0 > 0 || P.halo == 0);
   // history: whole sub-chunks, so that the searched range starts on a sub-chunk
   const uint64_t hmax = P.hist_max;
-  const uint64_t hist = restart ? 0 : ((s_lo - f_lo) < hmax ? ((s_lo - f_lo) & ~uint64_t(DF_SUB - 1)) : hmax);
+  // a stream with a preset dictionary: its first workgroup's history is the
+  // dictionary (D.dict: rel [0, hist), data from rel `floor` on), the stream
+  // follows at rel hist; h_lo may then lie before the buffer (modular
+  // arithmetic, no byte below rel hist is read through g)
+  const bool dfirst = DICT && s_lo == f_lo;
+  const uint64_t hist = dfirst    ? (uint64_t)D.hist
+                        : restart ? 0
+                                  : ((s_lo - f_lo) < hmax ? ((s_lo - f_lo) & ~uint64_t(DF_SUB - 1)) : hmax);
+  const uint32_t floor = dfirst ? D.floor : 0u;
   const uint64_t h_lo = s_lo - hist;
-  const uint8_t *g = P.base + h_lo;  // rel 0
+  const uint8_t *g = DICT ? reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(P.base) + h_lo)
+                          : P.base + h_lo;  // rel 0
+  // rel r's bytes: the dictionary below dsplit (a multiple of DF_SUB: no
+  // sub-chunk or head straddles it), else the stream
+  const uint32_t dsplit = dfirst ? D.hist : 0u;
+  const uint8_t *gd = dfirst ? D.dict : g;
+  // (DICT = false keeps the expressions g + r of the plain kernel as they were)
+  auto src = [&](uint32_t r) -> const uint8_t * { return (r < dsplit ? gd : g) + r; };
   const uint32_t rs = (uint32_t)(s_lo - h_lo), re = (uint32_t)(s_hi - h_lo);
   // bytes available for hashing: the stream's, but not past the end of the
   // super-chunk's segment (a restart point): positions near a segment end
@@ -1078,15 +1153,16 @@ __global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
   // workgroup, which made the output depend on the run)
   for (uint32_t i = t; i < DF_SUB; i += DF_THREADS) s.link4[i] = 0;
   __syncthreads();
-  uint32_t inserted = 0;  // positions [0, inserted) are in the chains
-  if (re > 0) load_sub(&s, g, 0, re < DF_SUB ? re : DF_SUB);
+  uint32_t inserted = floor;  // positions [floor, inserted) are in the chains
+  if (re > 0) load_sub(&s, DICT ? src(0) : g, 0, re < DF_SUB ? re : DF_SUB);
   // (the second sub-chunk's head: bytes [DF_SUB, DF_SUB + DF_HEAD); heads
   // run on past the super-chunk into the stream, so that a position at a
   // block end is linked and searched alike whatever the super-chunk size)
   if (DF_HEAD && t < (uint32_t)DF_HEAD && DF_SUB + t < rend) {
-    ring_put8(&s, ridx(DF_SUB + t), g[DF_SUB + t]);
+    ring_put8(&s, ridx(DF_SUB + t), DICT ? src(DF_SUB)[t] : g[DF_SUB + t]);
   }
-  const bool g_aligned = (reinterpret_cast<uintptr_t>(g) & 3) == 0;
+  const bool g_aligned =
+      ((reinterpret_cast<uintptr_t>(g) | (DICT ? reinterpret_cast<uintptr_t>(gd) : uintptr_t(0))) & 3) == 0;
   for (uint32_t p0 = 0; p0 < re; p0 += DF_SUB) {
     const uint32_t p1 = (p0 + DF_SUB) < re ? (p0 + DF_SUB) : re;
     lds_barrier();
@@ -1117,12 +1193,12 @@ __global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
     const uint32_t n0 = p0 + DF_SUB;
     const bool fast = g_aligned && n0 + DF_SUB <= re;
     uint32_t nv = 0;
-    if (fast) nv = reinterpret_cast<const uint32_t *>(g + n0)[t];
+    if (fast) nv = reinterpret_cast<const uint32_t *>(DICT ? src(n0) : g + n0)[t];
     // and the head of the one after it (written with nv, after the search)
     const uint32_t hd0 = n0 + DF_SUB;
     const bool hload = DF_HEAD && t < (uint32_t)DF_HEAD && hd0 + t < rend;
     uint8_t hb = 0;
-    if (hload) hb = g[hd0 + t];
+    if (hload) hb = DICT ? src(hd0)[t] : g[hd0 + t];
     // matches end at the block's end (or the data's)
     uint32_t pml = p1;
     if (DF_HEAD && p0 >= rs) {
@@ -1176,7 +1252,8 @@ __global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
 #ifdef ZT_DF_TIME
         DF_T(w1);
 #endif
-        search_quad(&s, P, p0 + 256 * ss + 4 * (t & 63), p0, p1, pml, ih, key, res_out, mc, late);
+        search_quad<DICT>(&s, P, p0 + 256 * ss + 4 * (t & 63), p0, p1, pml, ih, DICT ? floor : 0u, key, res_out, mc,
+                          late);
 #ifdef ZT_DF_TIME
         DF_T(w2);
         t_wait += w1 - w0;
@@ -1210,12 +1287,22 @@ __global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
     if (fast) {
       ring_put32(&s, (ridx(n0) >> 2) + t, nv);
     } else if (n0 < re) {
-      load_sub(&s, g + n0, n0, (re - n0) < DF_SUB ? (re - n0) : DF_SUB);
+      load_sub(&s, DICT ? src(n0) : g + n0, n0, (re - n0) < DF_SUB ? (re - n0) : DF_SUB);
     }
     if (hload) {
       ring_put8(&s, ridx(hd0 + t), hb);
     }
   }
+}
+
+__global__ __launch_bounds__(DF_THREADS) void match_kernel(DeflateParams P) {
+  __shared__ MatchShared s;
+  match_body<false>(P, DictView{}, s);
+}
+// batches with a preset dictionary
+__global__ __launch_bounds__(DF_THREADS) void match_dict_kernel(DeflateParams P, DictView D) {
+  __shared__ MatchShared s;
+  match_body<true>(P, D, s);
 }
 
 // ================================ 2. block_kernel ================================
@@ -2789,6 +2876,8 @@ static bool classify_on(int ctype) {
 
 // bytes per independent segment: a deflate call on a slice that starts at a
 // multiple of it (halo 0) writes that slice's part of the whole-buffer stream
+static_assert(kDictMaxTail == DF_MAXDIST && kDictSub == DF_SUB, "dict_host.h states the match kernel's geometry");
+
 size_t deflate_segment_bytes() { return (size_t)restart_blocks() * DF_BLOCK; }
 
 size_t deflate_bound_bytes(size_t n) {
@@ -2922,8 +3011,12 @@ size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded) {
 
 int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const uint64_t *off, const uint64_t *len,
                           int ctype, int level, uint8_t *d_out, uint64_t *out_off, void *scratch_base,
-                          size_t scratch_size, hipStream_t s) {
+                          size_t scratch_size, hipStream_t s, const DictHist *dict) {
   if (count == 0) return ZT_OK;
+  if (dict && dict->d_hist &&
+      (dict->hist == 0 || dict->hist % DF_SUB || dict->hist > (uint32_t)DF_HIST || dict->floor >= (uint32_t)DF_SUB ||
+       dict->hist - dict->floor > (uint32_t)DF_MAXDIST || (reinterpret_cast<uintptr_t>(dict->d_hist) & 3)))
+    return set_error(ZT_E_ARG, "invalid dictionary history");
   const uint64_t padded = off[count - 1] + ((len[count - 1] + DF_BLOCK - 1) / DF_BLOCK) * DF_BLOCK;
   DeflateGeom G;
   const size_t need = deflate_geometry(c, padded, &G);
@@ -2971,6 +3064,8 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   P.span = d_span;
+  const bool has_dict = dict && dict->d_hist;
+  const DictView DV{has_dict ? dict->d_hist : nullptr, has_dict ? dict->hist : 0u, has_dict ? dict->floor : 0u};
   P.res = reinterpret_cast<uint32_t *>(sb);
   P.slots = sb + G.res_bytes;
   P.slot_len = reinterpret_cast<uint32_t *>(sb + G.res_bytes + G.slot_bytes);
@@ -2983,11 +3078,17 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   P.fault = P.nstore + 1;
   ZT_HIP(hipMemsetAsync(P.nstore, 0, 8, s));
   if (P.store) {
-    classify_kernel<<<G.nblocks, 256, 0, s>>>(P);
+    if (has_dict)
+      classify_dict_kernel<<<G.nblocks, 256, 0, s>>>(P, DV);
+    else
+      classify_kernel<<<G.nblocks, 256, 0, s>>>(P);
     ZT_HIP(hipGetLastError());
   }
   ZT_TRY(timing_begin(c, s, 0));
-  match_kernel<<<G.nblocks, DF_THREADS, 0, s>>>(P);
+  if (has_dict)
+    match_dict_kernel<<<G.nblocks, DF_THREADS, 0, s>>>(P, DV);
+  else
+    match_kernel<<<G.nblocks, DF_THREADS, 0, s>>>(P);
   ZT_HIP(hipGetLastError());
   ZT_TRY(timing_end(c, s, 0));
   if (P.opt) {

@@ -206,9 +206,11 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
 int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
                               const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
                               int *status);
+// (d_hist / hist_len: a preset dictionary's window, in front of every stream's
+// output: the one-wave decoder only, InfJob::hist)
 static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
                              const size_t *index, size_t count, int strict, uint8_t **out, size_t *out_len,
-                             size_t *end_ip, int *status) {
+                             size_t *end_ip, int *status, const uint8_t *d_hist = nullptr, uint32_t hist_len = 0) {
   std::vector<size_t> cap(count);
   for (size_t i = 0; i < count; ++i) {
     // first guess (4x the stream's bytes from its start); exact sizes are
@@ -225,7 +227,7 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
   // non-strict batches of several streams: two-phase first, one wave per
   // stream for whatever it leaves (ZT_BATCH_ONEWAVE=1 forces the latter)
   static const bool onewave = getenv("ZT_BATCH_ONEWAVE") != nullptr;
-  if (!strict && count >= 8 && !onewave) {
+  if (!strict && count >= 8 && !onewave && !hist_len) {
     ZT_TRY(batch_two_phase(c, (const uint8_t *)d_in, in_off, n, index, count, out, out_len, res, todo));
     std::sort(todo.begin(), todo.end());
   } else {
@@ -251,6 +253,8 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
       jobs[k].out = (uint8_t *)d_out + out_off[k];
       jobs[k].cap = cap[i];
       jobs[k].strict = strict;
+      jobs[k].hist = d_hist;
+      jobs[k].hist_len = hist_len;
     }
     ZT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), todo.size() * sizeof(InfJob), hipMemcpyHostToDevice, c->stream));
     ZT_TRY(inflate_jobs_dev((const InfJob *)d_jobs, (InfResult *)d_res, (int)todo.size(), c->stream));
@@ -263,6 +267,7 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
     size_t span = 0;
     for (size_t k = 0; k < todo.size(); ++k) {
       size_t i = todo[k];
+      r[k].out_len -= hist_len;  // (the kernel counts the history as output [0, hist_len))
       res[i] = r[k];
       if (r[k].status == ZT_OK && r[k].out_len > cap[i]) {
         cap[i] = r[k].out_len;  // rerun with the exact size
@@ -310,7 +315,7 @@ int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<
 // Decode `count` host streams; outputs are malloc'd.
 static int inflate_host_batch(const uint8_t *const *in, const size_t *n, const size_t *index, size_t count,
                               const zt_inflate_opts *opts, uint8_t **out, size_t *out_len, size_t *end_ip,
-                              int *status) {
+                              int *status, const uint8_t *d_hist = nullptr, uint32_t hist_len = 0) {
   DeviceCtx *c;
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
@@ -343,7 +348,13 @@ static int inflate_host_batch(const uint8_t *const *in, const size_t *n, const s
     }
     BT("pack done");
   }
-  return inflate_dev_batch(c, d_in, in_off, n, index, count, strict, out, out_len, end_ip, status);
+  return inflate_dev_batch(c, d_in, in_off, n, index, count, strict, out, out_len, end_ip, status, d_hist, hist_len);
+}
+
+int inflate_host_batch_hist(const uint8_t *const *in, const size_t *n, const size_t *index, size_t count,
+                            const uint8_t *d_hist, uint32_t hist_len, uint8_t **out, size_t *out_len, size_t *end_ip,
+                            int *status) {
+  return inflate_host_batch(in, n, index, count, nullptr, out, out_len, end_ip, status, d_hist, hist_len);
 }
 
 // One device-resident stream from `index` (gzip / zlib members): the

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/zt.h"
+#include "dict_host.h"
 
 namespace zt {
 
@@ -62,12 +63,13 @@ struct DeviceCtx {
   uint32_t *d_crc_shift = nullptr;  // checksum.hip merge constants (crc_shift_tables)
   CkAcc *d_ck_acc = nullptr;        // checksum merge accumulators (zeroed once, left zeroed by every call)
   // scratch
-  static constexpr int kSlots = 29;
+  static constexpr int kSlots = 30;
   void *d_buf[kSlots] = {};  // slot 8: checksum segment partials; 10-17: general inflate (inflate_gen.hip);
                              // 20: segment inflate's sync-point sort (inflate_seg.hip); 21: stored runs;
                              // 22: pipelined host inflate's output, 23-25: its overflow ring (inflate_api.cpp);
                              // 26: general inflate's window pointer-jumping buffers; 27: framed batch members;
-                             // 28: segment inflate's tokenize launch order
+                             // 28: segment inflate's tokenize launch order; 29: a preset dictionary
+                             // (zt_dict.h: deflate history | inflate window | the whole dictionary)
   size_t buf_size[kSlots] = {};
   // second stream: checksums run beside the deflate pipeline in the containers
   hipStream_t aux = nullptr;
@@ -222,9 +224,29 @@ int current_device();                                                 // zt_api.
 std::vector<int> batch_devices();                                     // zt_set_devices, else {current}
 // batch deflate (deflate.hip): streams packed at 32 KiB boundaries, one pipeline
 size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded);
+// a preset dictionary as the match kernel reads it (dict_host.h: dict_layout):
+// d_hist[0 .. hist) on the device, 4-byte aligned, data from `floor` on
+struct DictHist {
+  const uint8_t *d_hist;
+  uint32_t hist, floor;
+};
 int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const uint64_t *off, const uint64_t *len,
                           int ctype, int level, uint8_t *d_out, uint64_t *out_off, void *scratch_base,
-                          size_t scratch_size, hipStream_t s);
+                          size_t scratch_size, hipStream_t s, const DictHist *dict = nullptr);
+// host dictionary (dict_api.cpp / batch_api.cpp): the batch deflate calls with
+// one dictionary for every buffer (dict_len == 0: none); zlib = FDICT framing
+// with this DICTID
+struct HostDict {
+  const uint8_t *dict = nullptr;
+  size_t dict_len = 0;
+};
+int deflate_batch_host(const uint8_t *const *in, const size_t *n, size_t count, const zt_deflate_opts *opts,
+                       const HostDict &hd, bool zlib, uint32_t dictid, uint8_t **out, size_t *out_len, int *status);
+// host streams decoded by one wave each with `hist_len` <= 32768 bytes of
+// device history d_hist in front of every stream (inflate_api.cpp)
+int inflate_host_batch_hist(const uint8_t *const *in, const size_t *n, const size_t *index, size_t count,
+                            const uint8_t *d_hist, uint32_t hist_len, uint8_t **out, size_t *out_len, size_t *end_ip,
+                            int *status);
 
 // ---- inflate jobs (one stream per wavefront) -----------------------------------
 struct InfJob {

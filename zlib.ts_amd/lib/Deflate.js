@@ -11,6 +11,10 @@ export class Deflate {
         this.compressionType = dflt(opts.compressionType, CompressionType.DYNAMIC);
         this.lazy = dflt(opts.lazy, 0);
         this.level = dflt(opts.level, 6);
+        // preset dictionary (Uint8Array), named as in Node's zlib; this build's
+        // extra option: the reference has none
+        this.dictionary = opts.dictionary == null ? undefined
+            : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
         this.adler32 = undefined;
     }
 
@@ -21,7 +25,7 @@ export class Deflate {
     compress() {
         let r;
         try {
-            r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level);
+            r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level, this.dictionary);
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';
             throw refError(e);

@@ -11,17 +11,22 @@ export class Inflate {
         this.ip = this.index;
         this.verify = dflt(opts.verify, false);
         this.adler32 = undefined;
+        // preset dictionary (Uint8Array), named as in Node's zlib; this build's
+        // extra option: the reference has none
+        this.dictionary = opts.dictionary == null ? undefined
+            : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
         const cmf = this.input[this.ip++];
         const flg = this.input[this.ip++];
         if ((cmf & 0x0f) != 8) throw new Error('unsupported compression method');
         if (((cmf << 8) + flg) % 31 !== 0) throw new Error('invalid fcheck flag:' + ((cmf << 8) + flg) % 31);
-        if (flg & 0x20) throw new Error('fdict flag is not supported');
+        // (with the `dictionary` option an FDICT stream is decoded: zt_zlib_decompress_dict)
+        if ((flg & 0x20) && !(this.dictionary && this.dictionary.length)) throw new Error('fdict flag is not supported');
     }
 
     decompress() {
         let r;
         try {
-            r = native.zlibDecompress(this.input, this.index, this.verify);
+            r = native.zlibDecompress(this.input, this.index, this.verify, this.dictionary);
         } catch (e) {
             throw refError(e);
         }

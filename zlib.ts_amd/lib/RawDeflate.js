@@ -13,6 +13,10 @@ export class RawDeflate {
         this.lazy = dflt(opts.lazy, 0);
         this.compressionType = dflt(opts.compressionType, CompressionType.DYNAMIC);
         this.level = dflt(opts.level, 6);
+        // preset dictionary (Uint8Array), named as in Node's zlib; this build's
+        // extra option: the reference has none
+        this.dictionary = opts.dictionary == null ? undefined
+            : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
         if (opts.outputBuffer) {
             this.output = opts.outputBuffer instanceof Uint8Array ? opts.outputBuffer : new Uint8Array(opts.outputBuffer);
         } else {
@@ -33,7 +37,7 @@ export class RawDeflate {
         }
         let stream;
         try {
-            stream = native.deflateRaw(this.input, ct, this.lazy, this.level);
+            stream = native.deflateRaw(this.input, ct, this.lazy, this.level, this.dictionary);
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';
             throw e;

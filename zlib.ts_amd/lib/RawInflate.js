@@ -16,6 +16,10 @@ export class RawInflate {
         this.bufferType = dflt(opts.bufferType, BufferType.ADAPTIVE);
         this.resize = dflt(opts.resize, false);
         this.refStrict = dflt(opts.refStrict, false);
+        // preset dictionary (Uint8Array), named as in Node's zlib; this build's
+        // extra option: the reference has none
+        this.dictionary = opts.dictionary == null ? undefined
+            : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
         this.buffer = null;
         this.output = new Uint8Array(0);
         this.op = 0;
@@ -27,7 +31,8 @@ export class RawInflate {
         }
         let r;
         try {
-            r = native.inflateRaw(this.input, this.ip, this.bufferType, this.bufferSize, this.refStrict);
+            r = native.inflateRaw(this.input, this.ip, this.bufferType, this.bufferSize, this.refStrict,
+                                  this.dictionary);
         } catch (e) {
             // libzt's message is the reference's text ('input buffer is broken', ...)
             throw new Error(e.message);

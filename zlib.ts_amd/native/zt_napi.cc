@@ -13,6 +13,7 @@
 
 #include "../../include/zt.h"
 #include "../../include/zt_zipcrypto.h"
+#include "../../include/zt_dict.h"
 
 namespace {
 
@@ -110,6 +111,20 @@ napi_value args(napi_env env, napi_callback_info info, napi_value *argv, size_t 
   return undef;
 }
 
+// optional trailing `dictionary` argument (include/zt_dict.h): undefined /
+// null = none (*given stays false)
+bool get_dict(napi_env env, napi_value v, const uint8_t **p, size_t *n, bool *given) {
+  napi_valuetype t;
+  napi_typeof(env, v, &t);
+  *given = false;
+  *p = nullptr;
+  *n = 0;
+  if (t == napi_undefined || t == napi_null) return true;
+  if (!get_u8(env, v, p, n)) return false;
+  *given = true;
+  return true;
+}
+
 // crc32Update(data: Uint8Array, crc: number) -> number
 napi_value crc32_update(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -140,10 +155,14 @@ napi_value adler32_update(napi_env env, napi_callback_info info) {
   return r;
 }
 
-// deflateRaw(input: Uint8Array, compressionType, lazy, level) -> Uint8Array
+// deflateRaw(input: Uint8Array, compressionType, lazy, level[, dictionary]) -> Uint8Array
 napi_value deflate_raw(napi_env env, napi_callback_info info) {
-  napi_value a[4];
-  args(env, info, a, 4);
+  napi_value a[5];
+  args(env, info, a, 5);
+  const uint8_t *d;
+  size_t dn;
+  bool has_d;
+  if (!get_dict(env, a[4], &d, &dn, &has_d)) return nullptr;
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -153,15 +172,19 @@ napi_value deflate_raw(napi_env env, napi_callback_info info) {
   o.level = (int)get_i64(env, a[3], -1);
   uint8_t *out = nullptr;
   size_t olen = 0;
-  int rc = zt_deflate_raw(p, n, &o, &out, &olen);
+  int rc = has_d ? zt_deflate_raw_dict(p, n, &o, d, dn, &out, &olen) : zt_deflate_raw(p, n, &o, &out, &olen);
   if (rc) return throw_zt(env, rc);
   return new_u8(env, out, olen);
 }
 
-// inflateRaw(input: Uint8Array, index, bufferType, bufferSize, refStrict) -> {output, ip}
+// inflateRaw(input: Uint8Array, index, bufferType, bufferSize, refStrict[, dictionary]) -> {output, ip}
 napi_value inflate_raw(napi_env env, napi_callback_info info) {
-  napi_value a[5];
-  args(env, info, a, 5);
+  napi_value a[6];
+  args(env, info, a, 6);
+  const uint8_t *d;
+  size_t dn;
+  bool has_d;
+  if (!get_dict(env, a[5], &d, &dn, &has_d)) return nullptr;
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -176,7 +199,9 @@ napi_value inflate_raw(napi_env env, napi_callback_info info) {
   o.ref_strict = strict ? 1 : 0;
   uint8_t *out = nullptr;
   size_t olen = 0, ip = 0;
-  int rc = zt_inflate_raw(p, n, index < 0 ? 0 : (size_t)index, &o, &out, &olen, &ip);
+  const size_t idx = index < 0 ? 0 : (size_t)index;
+  int rc = has_d ? zt_inflate_raw_dict(p, n, idx, &o, d, dn, &out, &olen, &ip)
+                 : zt_inflate_raw(p, n, idx, &o, &out, &olen, &ip);
   if (rc) return throw_zt(env, rc);
   napi_value obj, ipv;
   napi_create_object(env, &obj);
@@ -306,9 +331,14 @@ napi_value gunzip(napi_env env, napi_callback_info info) {
 }
 
 // zlibCompress(input, compressionType, lazy, level) -> {output, adler32}
+// (a fifth argument: the preset dictionary -- FDICT and DICTID in the header)
 napi_value zlib_compress(napi_env env, napi_callback_info info) {
-  napi_value a[4];
-  args(env, info, a, 4);
+  napi_value a[5];
+  args(env, info, a, 5);
+  const uint8_t *d;
+  size_t dn;
+  bool has_d;
+  if (!get_dict(env, a[4], &d, &dn, &has_d)) return nullptr;
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -319,7 +349,8 @@ napi_value zlib_compress(napi_env env, napi_callback_info info) {
   uint8_t *out = nullptr;
   size_t olen = 0;
   uint32_t adler = 1;
-  int rc = zt_zlib_compress(p, n, &o, &out, &olen, &adler);
+  int rc = has_d ? zt_zlib_compress_dict(p, n, &o, d, dn, &out, &olen, &adler)
+                 : zt_zlib_compress(p, n, &o, &out, &olen, &adler);
   if (rc) return throw_zt(env, rc);
   napi_value obj;
   napi_create_object(env, &obj);
@@ -328,10 +359,14 @@ napi_value zlib_compress(napi_env env, napi_callback_info info) {
   return obj;
 }
 
-// zlibDecompress(input, index, verify) -> {output, ip, adler32}
+// zlibDecompress(input, index, verify[, dictionary]) -> {output, ip, adler32}
 napi_value zlib_decompress(napi_env env, napi_callback_info info) {
-  napi_value a[3];
-  args(env, info, a, 3);
+  napi_value a[4];
+  args(env, info, a, 4);
+  const uint8_t *d;
+  size_t dn;
+  bool has_d;
+  if (!get_dict(env, a[3], &d, &dn, &has_d)) return nullptr;
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -343,7 +378,9 @@ napi_value zlib_decompress(napi_env env, napi_callback_info info) {
   uint8_t *out = nullptr;
   size_t olen = 0, ip = 0;
   uint32_t adler = 1;
-  int rc = zt_zlib_decompress(p, n, index < 0 ? 0 : (size_t)index, verify, &out, &olen, &ip, &adler);
+  const size_t idx = index < 0 ? 0 : (size_t)index;
+  int rc = has_d ? zt_zlib_decompress_dict(p, n, idx, verify, d, dn, &out, &olen, &ip, &adler)
+                 : zt_zlib_decompress(p, n, idx, verify, &out, &olen, &ip, &adler);
   if (rc) return throw_zt(env, rc);
   napi_value obj;
   napi_create_object(env, &obj);

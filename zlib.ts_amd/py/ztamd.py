@@ -17,7 +17,7 @@ ERRORS = {
     -15: "ZT_E_INVALID_DISTANCE", -16: "ZT_E_INVALID_SYMBOL", -17: "ZT_E_BAD_TREE",
     -30: "ZT_E_GZIP_SIGNATURE", -31: "ZT_E_GZIP_METHOD", -32: "ZT_E_GZIP_HCRC", -33: "ZT_E_GZIP_CRC32",
     -34: "ZT_E_GZIP_ISIZE", -40: "ZT_E_ZLIB_METHOD", -41: "ZT_E_ZLIB_FCHECK", -42: "ZT_E_ZLIB_FDICT",
-    -43: "ZT_E_ZLIB_ADLER", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED", -100: "ZT_E_NO_DEVICE",
+    -43: "ZT_E_ZLIB_ADLER", -44: "ZT_E_ZLIB_DICTID", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED", -100: "ZT_E_NO_DEVICE",
     -101: "ZT_E_HIP", -102: "ZT_E_NOMEM", -103: "ZT_E_ARG", -104: "ZT_E_INTERNAL",
 }
 
@@ -145,6 +145,17 @@ def _load():
         "zt_zipcrypto_last_kernel_ms": ([P(ctypes.c_double)], ctypes.c_int),
         "zt_zip_compress_pw": ([P(vp), P(sz), P(ZipFile), P(ZipCrypt), sz, vp, sz, u8pp, P(sz)], ctypes.c_int),
         "zt_unzip_pw": ([vp, sz, ctypes.c_int, vp, sz, u8pp, P(sz), P(P(UnzipEntry)), P(sz)], ctypes.c_int),
+        # include/zt_dict.h
+        "zt_deflate_raw_dict": ([vp, sz, P(DeflateOpts), vp, sz, u8pp, P(sz)], ctypes.c_int),
+        "zt_inflate_raw_dict": ([vp, sz, sz, P(InflateOpts), vp, sz, u8pp, P(sz), P(sz)], ctypes.c_int),
+        "zt_deflate_raw_batch_dict": ([P(vp), P(sz), sz, P(DeflateOpts), vp, sz, u8pp, P(sz), P(ctypes.c_int)],
+                                      ctypes.c_int),
+        "zt_inflate_raw_batch_dict": ([P(vp), P(sz), sz, P(InflateOpts), vp, sz, u8pp, P(sz), P(sz),
+                                       P(ctypes.c_int)], ctypes.c_int),
+        "zt_zlib_compress_dict": ([vp, sz, P(DeflateOpts), vp, sz, u8pp, P(sz), P(u32)], ctypes.c_int),
+        "zt_zlib_compress_batch_dict": ([P(vp), P(sz), sz, P(DeflateOpts), vp, sz, u8pp, P(sz), P(ctypes.c_int)],
+                                        ctypes.c_int),
+        "zt_zlib_decompress_dict": ([vp, sz, sz, ctypes.c_int, vp, sz, u8pp, P(sz), P(sz), P(u32)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -174,6 +185,12 @@ SYMBOLS = [
 ZIPCRYPTO_SYMBOLS = [
     "zt_zipcrypto_encrypt_batch", "zt_zipcrypto_decrypt_batch", "zt_zipcrypto_tile_bytes",
     "zt_zipcrypto_chunk_bytes", "zt_zipcrypto_last_kernel_ms", "zt_zip_compress_pw", "zt_unzip_pw",
+]
+
+# every symbol include/zt_dict.h declares (checked by tests/test_dict_host.py)
+DICT_SYMBOLS = [
+    "zt_deflate_raw_dict", "zt_inflate_raw_dict", "zt_deflate_raw_batch_dict", "zt_inflate_raw_batch_dict",
+    "zt_zlib_compress_dict", "zt_zlib_compress_batch_dict", "zt_zlib_decompress_dict",
 ]
 
 
@@ -221,26 +238,36 @@ def checksums(data, crc=0, adler=1):
     return c.value, a.value
 
 
-def deflate_raw(data, compression_type=2, lazy=0, level=-1):
+def deflate_raw(data, compression_type=2, lazy=0, level=-1, dictionary=None):
+    """dictionary: preset dictionary (zlib's zdict), include/zt_dict.h."""
     b, n = _cbuf(data)
     opts = DeflateOpts(compression_type, lazy, level)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
-    _check(lib.zt_deflate_raw(b, n, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(olen)))
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        _check(lib.zt_deflate_raw_dict(b, n, ctypes.byref(opts), d, dn, ctypes.byref(out), ctypes.byref(olen)))
+    else:
+        _check(lib.zt_deflate_raw(b, n, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(olen)))
     res = ctypes.string_at(out, olen.value)
     lib.zt_free(out)
     return res
 
 
-def inflate_raw(data, index=0, ref_strict=False, buffer_type=1, buffer_size=0x8000):
+def inflate_raw(data, index=0, ref_strict=False, buffer_type=1, buffer_size=0x8000, dictionary=None):
     """Returns (output bytes, end ip)."""
     b, n = _cbuf(data)
     opts = InflateOpts(buffer_type, buffer_size, 1 if ref_strict else 0)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     ip = ctypes.c_size_t()
-    _check(lib.zt_inflate_raw(b, n, index, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(olen),
-                              ctypes.byref(ip)))
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        _check(lib.zt_inflate_raw_dict(b, n, index, ctypes.byref(opts), d, dn, ctypes.byref(out),
+                                       ctypes.byref(olen), ctypes.byref(ip)))
+    else:
+        _check(lib.zt_inflate_raw(b, n, index, ctypes.byref(opts), ctypes.byref(out), ctypes.byref(olen),
+                                  ctypes.byref(ip)))
     res = ctypes.string_at(out, olen.value)
     lib.zt_free(out)
     return res, ip.value
@@ -305,7 +332,7 @@ class RawInflateStream:
         return out
 
 
-def inflate_raw_batch(streams, ref_strict=False):
+def inflate_raw_batch(streams, ref_strict=False, dictionary=None):
     """Returns a list of (status, output bytes, end ip)."""
     k = len(streams)
     # the bytes objects' own buffers are passed (no copy); `bs` keeps them alive
@@ -317,7 +344,11 @@ def inflate_raw_batch(streams, ref_strict=False):
     ips = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
     opts = InflateOpts(1, 0x8000, 1 if ref_strict else 0)
-    rc = lib.zt_inflate_raw_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, ips, st)
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        rc = lib.zt_inflate_raw_batch_dict(ptrs, lens, k, ctypes.byref(opts), d, dn, outs, olens, ips, st)
+    else:
+        rc = lib.zt_inflate_raw_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, ips, st)
     if rc != ZT_OK and all(s == 0 for s in st):
         _check(rc)
     res = []
@@ -329,7 +360,7 @@ def inflate_raw_batch(streams, ref_strict=False):
     return res
 
 
-def deflate_raw_batch(items, compression_type=2, level=-1):
+def deflate_raw_batch(items, compression_type=2, level=-1, dictionary=None):
     k = len(items)
     bufs = [_cbuf(s) for s in items]
     ptrs = (ctypes.c_void_p * k)(*[ctypes.addressof(b) for b, _ in bufs])
@@ -338,7 +369,11 @@ def deflate_raw_batch(items, compression_type=2, level=-1):
     olens = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
     opts = DeflateOpts(compression_type, 0, level)
-    rc = lib.zt_deflate_raw_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, st)
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        rc = lib.zt_deflate_raw_batch_dict(ptrs, lens, k, ctypes.byref(opts), d, dn, outs, olens, st)
+    else:
+        rc = lib.zt_deflate_raw_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, st)
     _check(rc)
     res = []
     for i in range(k):
@@ -406,14 +441,18 @@ def gzip_compress_batch(items, name=None, comment=None, hcrc=False, mtime=0, com
     return _batch_take(k, outs, olens)
 
 
-def zlib_compress_batch(items, compression_type=2, lazy=0, level=-1):
+def zlib_compress_batch(items, compression_type=2, lazy=0, level=-1, dictionary=None):
     bs, ptrs, lens = _batch_ptrs(items)
     k = len(bs)
     opts = DeflateOpts(compression_type, lazy, level)
     outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
     olens = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
-    _check(lib.zt_zlib_compress_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, st))
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        _check(lib.zt_zlib_compress_batch_dict(ptrs, lens, k, ctypes.byref(opts), d, dn, outs, olens, st))
+    else:
+        _check(lib.zt_zlib_compress_batch(ptrs, lens, k, ctypes.byref(opts), outs, olens, st))
     return _batch_take(k, outs, olens)
 
 
@@ -584,26 +623,39 @@ def gunzip(data):
     return res, members
 
 
-def zlib_compress(data, compression_type=2, lazy=0, level=-1):
-    """Deflate.compress (src/Deflate.ts:60-99).  Returns (stream, adler32)."""
+def zlib_compress(data, compression_type=2, lazy=0, level=-1, dictionary=None):
+    """Deflate.compress (src/Deflate.ts:60-99).  Returns (stream, adler32).
+    dictionary: the stream carries FDICT and the dictionary's Adler-32."""
     b, n = _cbuf(data)
     o = DeflateOpts(compression_type, lazy, level)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     adler = ctypes.c_uint32()
-    _check(lib.zt_zlib_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(adler)))
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        _check(lib.zt_zlib_compress_dict(b, n, ctypes.byref(o), d, dn, ctypes.byref(out), ctypes.byref(olen),
+                                         ctypes.byref(adler)))
+    else:
+        _check(lib.zt_zlib_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen),
+                                    ctypes.byref(adler)))
     return _take(out, olen), adler.value
 
 
-def zlib_decompress(data, index=0, verify=False):
-    """Inflate.decompress (src/Inflate.ts:34-93).  Returns (output, ip)."""
+def zlib_decompress(data, index=0, verify=False, dictionary=None):
+    """Inflate.decompress (src/Inflate.ts:34-93).  Returns (output, ip).
+    dictionary: used when the stream carries FDICT (ignored otherwise)."""
     b, n = _cbuf(data)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     ip = ctypes.c_size_t()
     adler = ctypes.c_uint32()
-    _check(lib.zt_zlib_decompress(b, n, index, int(verify), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(ip),
-                                  ctypes.byref(adler)))
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        _check(lib.zt_zlib_decompress_dict(b, n, index, int(verify), d, dn, ctypes.byref(out), ctypes.byref(olen),
+                                           ctypes.byref(ip), ctypes.byref(adler)))
+    else:
+        _check(lib.zt_zlib_decompress(b, n, index, int(verify), ctypes.byref(out), ctypes.byref(olen),
+                                      ctypes.byref(ip), ctypes.byref(adler)))
     return _take(out, olen), ip.value
 
 
