@@ -7,14 +7,16 @@
 //      consecutive 32 KiB blocks; a 1 MiB segment starts without history,
 //      later super-chunks index the 28 KiB before them first).  4 KiB
 //      sub-chunks stream through a 32 KiB LDS ring (28 608-byte window).
-//      Wave 0 links 8-byte-key hash chains (u32 heads, u16 relative links)
+//      Wave 0 links 8-byte-key hash chains (u16 heads, u16 relative links)
 //      and wave 1 a 4-byte-key table (the newest earlier position per
 //      bucket), each by lane-ordered LDS exchanges head[h] <-> p, 64
 //      positions per exchange, publishing their progress; all waves search
 //      256-position super-steps as soon as they are linked: per thread 4
 //      positions, two chain walks interleaved (two LDS loads per hop: the
 //      link and one filter word), candidates measured against 16 bytes held
-//      in registers; matches shorter than the key come from near probes
+//      in registers -- at once, or, in blocks whose first sub-chunk measured
+//      many, 64 at a time through a per-wave LDS queue (the same matches);
+//      matches shorter than the key come from near probes
 //      (distances 1..16, register window) and the 4-byte table.  The
 //      longest match of every position goes to HBM: res[i] = len << 16 |
 //      dist.
@@ -54,7 +56,10 @@ __device__ unsigned long long g_bk_time[8];  // debug: block_kernel phase cycles
 #ifdef ZT_DF_COUNT
 __device__ unsigned long long g_df_count[8];  // debug: pair steps (per wave), lane hops, extends (lanes), extends (waves),
                                               // measured lanes that improve / measure < 8 bytes / do not improve
+                                              // (at once only), candidates queued (of the extends)
 #endif
+// blocks whose later sub-chunks measured through the queues / at once (zt_debug_match_modes)
+__device__ unsigned long long g_match_modes[2];
 
 #ifndef ZT_DF_BLOCK
 #define ZT_DF_BLOCK 32768
@@ -81,15 +86,13 @@ constexpr int DF_RING = 32768;  // power of two: ring index = rel & (DF_RING - 1
 // 17 + 19 * 3 + 316 * 14 bits); the coded block itself goes straight into the stream
 constexpr int DF_SLOT = 2048;
 static_assert(DF_SLOT >= 321 * 4 && DF_SLOT * 8 >= 17 + 19 * 3 + 316 * 14, "slot holds histograms and a header");
-// hash buckets of the 8-byte-key chains (u32 heads) and of the 4-byte-key
-// table (u32 heads, no chains): the sizes fill the 160 KiB of LDS next to the
-// ring, the chain links and the sub-chunk's 4-byte links
+// hash buckets of the 8-byte-key chains (u16 heads) and of the 4-byte-key
+// table (u32 heads, no chains): with the ring, the chain links, the
+// sub-chunk's 4-byte links and the waves' measurement queues they fill the
+// 160 KiB of LDS (u32 chain heads at the same count give the same streams;
+// their upper halves are the room the queues take)
 #ifndef ZT_DF_HSIZE
-#ifdef ZT_DF_HEAD16
-#define ZT_DF_HSIZE 24528  // (u16 heads, two per word)
-#else
-#define ZT_DF_HSIZE 12240
-#endif
+#define ZT_DF_HSIZE 12240  // (even: two u16 heads per word)
 #endif
 #ifndef ZT_DF_H4SIZE
 #define ZT_DF_H4SIZE 2048
@@ -100,6 +103,7 @@ static_assert(DF_SLOT >= 321 * 4 && DF_SLOT * 8 >= 17 + 19 * 3 + 316 * 14, "slot
 constexpr uint32_t DF_HSIZE = ZT_DF_HSIZE;
 constexpr uint32_t DF_H4SIZE = ZT_DF_H4SIZE;
 static_assert(DF_HSIZE <= 65536 && DF_H4SIZE <= 65536, "bucket indices are parked in u16 slots (hash_keys)");
+static_assert(DF_HSIZE % 2 == 0, "two u16 heads per word");
 constexpr int DF_THREADS = 1024;
 // the ring holds [p1 - DF_RING, p1) while sub-chunk [p0, p1) is searched;
 // a super-chunk loads DF_HIST bytes of history first (whole sub-chunks)
@@ -153,6 +157,11 @@ struct DeflateParams {
   // adapt_depth2 hops (match_kernel)
   int adapt_depth, adapt_thr;
   int adapt_depth2, adapt_thr2;
+  // Per-block candidate measurement (0: never queued): when the probe
+  // sub-chunk measured at least mq_thr candidates per 4096 positions, the
+  // rest of the block measures through the waves' queues (mq_pair_loop): the
+  // same matches, found with fuller waves
+  int mq_thr;
   // batch of independent streams (zt_deflate_batch_dev): stream f occupies
   // whole blocks from a 32 KiB-aligned offset; per block the [start, end) of
   // its stream (relative to halo = 0), or null for one stream of n bytes
@@ -516,24 +525,34 @@ __global__ __launch_bounds__(256) void classify_dict_kernel(DeflateParams P, Dic
 
 // ================================ 1. match_kernel ================================
 constexpr uint32_t RING_ENT = DF_RING / 4;
+constexpr uint32_t MQ_RING = 128;   // a wave's queue: two pushes of up to 64 between passes (walk_pair_hop_mq)
+constexpr uint32_t MQ_SLOTS = 128;  // a wave's walks in flight: two per lane
+#ifndef ZT_DF_MQ_FLUSH
+#define ZT_DF_MQ_FLUSH 15
+#endif
+// 2^k - 1: a short queue is measured every 2^k steps all the same (every 4 /
+// 8 / 16 steps at level 6: wordsalad 43.1 / 40.1 / 39.7, source text 44.5 /
+// 43.1 / 42.0 ms of match per GiB)
+constexpr int MQ_FLUSH = ZT_DF_MQ_FLUSH;
 struct MatchShared {
   uint32_t ring[DF_RING / 4 + 16];  // data ring + 64-byte mirror of its start
   uint16_t prev[DF_RING];           // relative chain links (0 = none)
-#ifdef ZT_DF_HEAD16
   uint32_t head[DF_HSIZE / 2];      // newest position (rel mod 2^16) per hash bucket, two buckets per word
-#else
-  uint32_t head[DF_HSIZE];          // newest position (rel) per hash bucket
-#endif
   uint32_t head4[DF_H4SIZE];        // newest position (rel) per 4-byte-key bucket
   uint16_t link4[DF_SUB];           // position p of the sub-chunk: distance to the newest earlier
                                     // position of its 4-byte-key bucket (0 = none), at p % DF_SUB
+  uint32_t mq[DF_THREADS / 64][MQ_RING];       // per wave: candidates to measure (distance | walk slot << 16), a ring
+  uint32_t mr[DF_THREADS / 64][MQ_SLOTS];      // per wave and walk slot: the best candidate's mq_key
   uint32_t dummy[4];                // exchange / link targets of lanes past the end (branch-free chain_link)
   uint32_t linked;                  // positions below are linked (chain_link -> searching waves)
   uint32_t linked4;                 // positions below have their 4-byte links
   uint32_t work;                    // next super-step of 256 positions to search
   uint32_t late, late2;             // probe sub-chunk: improvements at hop >= adapt_depth / adapt_depth2
+  uint32_t nmeas;                   // probe sub-chunk: candidates measured
   int depth;                        // max_chain of the block's later sub-chunks
+  int queued;                       // the block's later sub-chunks measure their candidates through the queues
 };
+static_assert(sizeof(MatchShared) <= 160 * 1024, "MatchShared fits the CU's LDS");
 
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
 // operations, not for its global loads (the next sub-chunk's prefetch stays
@@ -680,7 +699,6 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
     // branch-free: lanes past hi exchange with / link into a dummy word, so
     // the compiler keeps every load and exchange of the group in flight
     uint32_t old[CL_U];
-#ifdef ZT_DF_HEAD16
     if (T == 0) {
       // u16 heads: a masked-OR exchange of one half-word (ds_mskor_rtn_b32
       // applies a wave's conflicting lanes in lane order, as the exchange
@@ -695,6 +713,9 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
         const uint32_t a = (uint32_t)(uintptr_t)hp, clr = 0xFFFFu << sh[j], set = (p & 0xFFFFu) << sh[j];
         __asm__ volatile("ds_mskor_rtn_b32 %0, %1, %2, %3" : "=v"(old[j]) : "v"(a), "v"(clr), "v"(set) : "memory");
       }
+      // (the next group's hashes load while the exchanges are in flight; the
+      // wait below covers both)
+      hashes(sb + CL_U, hq);
       static_assert(CL_U == 8, "the wait below names 8 results");
       __asm__ volatile("s_waitcnt lgkmcnt(0)"
                        : "+v"(old[0]), "+v"(old[1]), "+v"(old[2]), "+v"(old[3]), "+v"(old[4]), "+v"(old[5]),
@@ -705,17 +726,15 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
         // (the distance modulo 2^16 is exact: stale heads are re-aged by head_sweep)
         old[j] = p - ((p - (old[j] >> sh[j])) & 0xFFFFu);
       }
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
       for (int j = 0; j < CL_U; ++j) {
         const uint32_t p = lo + (sb + j) * 64 + lane;
-        uint32_t *hp = p < hi ? (T == 0 ? &s->head[hq[j]] : &s->head4[hq[j]]) : &s->dummy[T];
+        uint32_t *hp = p < hi ? &s->head4[hq[j]] : &s->dummy[T];
         old[j] = atomicExch(hp, p);
       }
+      hashes(sb + CL_U, hq);
     }
-    hashes(sb + CL_U, hq);
 #pragma unroll
     for (int j = 0; j < CL_U; ++j) {
       const uint32_t p = lo + (sb + j) * 64 + lane;
@@ -731,14 +750,16 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
   }
 }
 
-#ifdef ZT_DF_HEAD16
 // u16 heads hold rel positions modulo 2^16: every HEAD_SWEEP sub-chunks, at
 // rel position S (before that sub-chunk is linked), a head that is out of
 // reach (age > DF_MAXDIST, and not one of the <= DF_HEAD positions linked
 // ahead of S) is re-aged to S - 32768: until the next sweep it reads as
 // 32768..61440 back -- never a link -- and a head in reach stays below 2^16
 // back until then, so every link the exchange computes is the true distance.
-constexpr uint32_t HEAD_SWEEP = 4;
+#ifndef ZT_DF_HEAD_SWEEP
+#define ZT_DF_HEAD_SWEEP 4
+#endif
+constexpr uint32_t HEAD_SWEEP = ZT_DF_HEAD_SWEEP;
 static_assert(DF_MAXDIST + (HEAD_SWEEP + 1) * DF_SUB + DF_HEAD < 65536 - 1024, "ages stay below 2^16");
 __device__ __forceinline__ void head_sweep(MatchShared *s, uint32_t S) {
   const uint32_t stale = (S - 32768u) & 0xFFFFu;
@@ -753,7 +774,6 @@ __device__ __forceinline__ void head_sweep(MatchShared *s, uint32_t S) {
     if (r != w) s->head[i] = r;
   }
 }
-#endif
 
 // 4 bytes at byte x of a register window (x a compile-time constant after unrolling)
 template <int X>
@@ -811,9 +831,18 @@ struct Walk {
   uint32_t p, q, link, max_len, best_len, best_dist, o, pw, omask, cur, cur2, cur3, cur4;
   uint32_t cl;  // carried match length (kept unless the walk finds one at least as long, nearer)
   int max_hops;  // (hops taken = the pair loop's step count while the walk is active)
-  uint32_t late; // improvements found at hop >= P.adapt_depth (low half) / adapt_depth2 (high half)
+  uint32_t late;  // ROLE_PROBE: improvements found at hop >= P.adapt_depth (low half) / adapt_depth2 (high half)
+  uint32_t nmeas; // ROLE_PROBE: candidates measured
   bool active;
 };
+
+// What a sub-chunk's walks do besides finding matches, fixed at compile time
+// (nothing is decided per hop).  The block's first sub-chunk is the probe: it
+// measures each candidate at once, walks max_chain hops and counts (late
+// improvements for the block's depth, measurements for the block's way of
+// measuring).  The others carry no counts and measure at once (plain) or
+// through the wave's queue (queued), as the probe's counts say.
+enum Role { ROLE_PROBE, ROLE_PLAIN, ROLE_QUEUED };
 
 // n words at byte rel of the ring, unaligned (the 64-byte mirror past the
 // ring's end keeps up to 15 words contiguous): n + 1 dword loads, no wrap math
@@ -898,8 +927,9 @@ __device__ __forceinline__ uint32_t eq_len16(uint32_t x0, uint32_t x1, uint32_t 
 
 // a candidate q that passed the one-word filter: its length from byte 0
 // (the filter checked at most 4 bytes) and keep the longest
+template <Role R>
 __device__ __forceinline__ void walk_extend(Walk &w, const MatchShared *s, const DeflateParams &P, uint32_t q,
-                                            uint32_t late) {
+                                            [[maybe_unused]] uint32_t late) {
 #ifdef ZT_DF_COUNT
   atomicAdd(&g_df_count[2], 1ull);
   // (wave-level executions of the measurement: its first active lane counts)
@@ -931,7 +961,10 @@ __device__ __forceinline__ void walk_extend(Walk &w, const MatchShared *s, const
 #endif
   const bool stop = upd && ((int)len >= P.nice_len || len >= w.max_len);
   const bool newo = upd && !stop && len >= 4;
-  w.late += upd ? late : 0u;
+  if constexpr (R == ROLE_PROBE) {
+    w.late += upd ? late : 0u;
+    w.nmeas += 1;
+  }
   w.best_len = upd ? len : w.best_len;
   w.best_dist = upd ? w.p - q : w.best_dist;
   w.active = w.active && !stop;
@@ -950,6 +983,7 @@ __device__ __forceinline__ void walk_extend(Walk &w, const MatchShared *s, const
 // active walk has taken exactly that many hops.  Inactive walks keep
 // stepping through stale links: their loads stay inside the ring and are
 // never used.
+template <Role R>
 __device__ __forceinline__ void walk_pair_step(Walk &a, Walk &b, const MatchShared *s, const DeflateParams &P,
                                                int step) {
   const uint32_t qa = a.q - a.link;
@@ -975,14 +1009,177 @@ __device__ __forceinline__ void walk_pair_step(Walk &a, Walk &b, const MatchShar
 #if defined(ZT_DF_X_EXT0)
   // (measurement build: candidates measured at the first hop only -- wrong
   // streams; the time without the later, divergent measurement passes)
-  if (ca && step == 0) walk_extend(a, s, P, qa, 0);
-  if (cb && step == 0) walk_extend(b, s, P, qb, 0);
+  if (ca && step == 0) walk_extend<R>(a, s, P, qa, 0);
+  if (cb && step == 0) walk_extend<R>(b, s, P, qb, 0);
 #else
-  const uint32_t late = (P.adapt_depth && step >= P.adapt_depth ? 1u : 0u) |
-                        (P.adapt_depth2 && step >= P.adapt_depth2 ? 0x10000u : 0u);
-  if (ca) walk_extend(a, s, P, qa, late);
-  if (cb) walk_extend(b, s, P, qb, late);
+  uint32_t late = 0;
+  if constexpr (R == ROLE_PROBE)
+    late = (P.adapt_depth && step >= P.adapt_depth ? 1u : 0u) |
+           (P.adapt_depth2 && step >= P.adapt_depth2 ? 0x10000u : 0u);
+  if (ca) walk_extend<R>(a, s, P, qa, late);
+  if (cb) walk_extend<R>(b, s, P, qb, late);
 #endif
+}
+
+// ---- ROLE_QUEUED: candidate measurement through a per-wave queue ----
+// Measured at once, the wave runs the measurement whenever any of its 128
+// walks has a candidate: on text 1.5 passes per pair step with 4.7 lanes
+// each, about as much time as the hops themselves.  Here a hop's candidate
+// (it passed the filter) is appended to the wave's ring instead.  Whenever 64
+// are queued, one pass measures 64 with every lane (p's bytes from the ring)
+// and keeps the best per walk in the walk's result slot by an LDS atomicMax
+// on mq_key: the longest, then the nearest -- the walk's own order (newest
+// first, the first of equal length kept).  The walks then read their slots
+// back and tighten their filters; until then a walk filters with an older
+// best, which only lets through more candidates (measured, and never longer
+// than the best).  Lengths enter the key clamped at nice_len: the walk at
+// once stops at the first such candidate, and the nearest of them is that
+// one; its owner measures its exact length again (mq_poll).  The ring is
+// FIFO, so a slot always holds the best of a prefix of its walk's candidates.
+// The streams are the ones of measuring at once.
+struct MqState {
+  uint32_t head, tail;  // wave-uniform: entries [head, tail) of the ring are queued
+  uint32_t pbase;       // position of lane 0's first walk of the pair (slot 0)
+  uint32_t pml;         // matches end here (wave-uniform)
+  bool ready;           // a pass has run since the walks last read their slots
+};
+__device__ __forceinline__ uint32_t mq_key(uint32_t len, uint32_t dist) { return (len << 15) | (0x7FFFu - dist); }
+static_assert(DF_MAXDIST < 0x7FFF, "a distance fits the key's low 15 bits and the ring entry's low 16");
+
+// walk `slot` of each lane with c set queues its candidate at distance dist
+__device__ __forceinline__ void mq_push(MatchShared *s, MqState &m, bool c, uint32_t dist, uint32_t slot) {
+  const uint64_t b = __ballot(c);
+  if (b) {
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
+    if (c) s->mq[threadIdx.x >> 6][(m.tail + below) & (MQ_RING - 1)] = dist | (slot << 16);
+#ifdef ZT_DF_COUNT
+    if (c) atomicAdd(&g_df_count[7], 1ull);
+#endif
+    m.tail += (uint32_t)__popcll(b);
+  }
+}
+
+// equal leading bytes of q.. and p.., 16 per round, at most max_len
+__device__ __forceinline__ uint32_t mq_measure(const MatchShared *s, uint32_t q, uint32_t p, uint32_t max_len) {
+  uint32_t len = 0;
+  bool more = true;
+  while (more && len < max_len) {
+    uint32_t qx[4], px[4];
+    ld_run<4>(s, q + len, qx);
+    ld_run<4>(s, p + len, px);
+    const uint32_t l = eq_len16(qx[0] ^ px[0], qx[1] ^ px[1], qx[2] ^ px[2], qx[3] ^ px[3]);
+    len += l;
+    more = l == 16;
+  }
+  return len < max_len ? len : max_len;
+}
+
+// one pass: the next min(64, queued) candidates, one per lane
+__device__ __forceinline__ void mq_process(MatchShared *s, const DeflateParams &P, MqState &m) {
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const uint32_t n = (m.tail - m.head) < 64u ? (m.tail - m.head) : 64u;
+  __builtin_amdgcn_wave_barrier();  // (the pushes are in the ring: the wave's LDS operations stay in order)
+#ifdef ZT_DF_COUNT
+  if (lane == 0) atomicAdd(&g_df_count[3], 1ull);
+#endif
+  if (lane < n) {
+#ifdef ZT_DF_COUNT
+    atomicAdd(&g_df_count[2], 1ull);
+#endif
+    const uint32_t e = s->mq[wv][(m.head + lane) & (MQ_RING - 1)];
+    const uint32_t dist = e & 0xFFFFu, slot = e >> 16;
+    // (slot 2 * l is the first walk of lane l's pair, 2 * l + 1 the second, two positions on)
+    const uint32_t p = m.pbase + 4 * (slot >> 1) + 2 * (slot & 1);
+    const uint32_t ml = p < m.pml ? ((m.pml - p) < 258u ? (m.pml - p) : 258u) : 0u;
+    const uint32_t len = mq_measure(s, p - dist, p, ml);
+    const uint32_t lk = len < (uint32_t)P.nice_len ? len : (uint32_t)P.nice_len;
+    if (len >= 3) atomicMax(&s->mr[wv][slot & (MQ_SLOTS - 1)], mq_key(lk, dist));
+  }
+  __builtin_amdgcn_wave_barrier();
+  m.head += n;
+  m.ready = true;
+}
+
+// walk_pair_step with the candidates queued instead of measured
+__device__ __forceinline__ void walk_pair_hop_mq(Walk &a, Walk &b, MatchShared *s, const DeflateParams &P, int step,
+                                                 MqState &m) {
+  const uint32_t qa = a.q - a.link;
+  const uint32_t qb = b.q - b.link;
+  const bool ha = a.active && a.p - qa <= (uint32_t)DF_MAXDIST;
+  const bool hb = b.active && b.p - qb <= (uint32_t)DF_MAXDIST;
+  const uint32_t la = s->prev[ridx(qa)], lb = s->prev[ridx(qb)];
+  const uint32_t oa = ld32(s, qa + a.o), ob = ld32(s, qb + b.o);
+  a.q = qa;
+  b.q = qb;
+#ifdef ZT_DF_COUNT
+  if ((threadIdx.x & 63) == 0) atomicAdd(&g_df_count[0], 1ull);
+  atomicAdd(&g_df_count[1], (unsigned long long)(ha ? 1 : 0) + (hb ? 1 : 0));
+#endif
+  const bool ca = ha & (((oa ^ a.pw) & a.omask) == 0);
+  const bool cb = hb & (((ob ^ b.pw) & b.omask) == 0);
+  a.link = la;
+  b.link = lb;
+  a.active = ha && la != 0 && step + 1 < a.max_hops;
+  b.active = hb && lb != 0 && step + 1 < b.max_hops;
+  // (a pass after either push whenever 64 are queued: fewer than 64 stay, so
+  // a push of at most 64 never overruns the ring of 128)
+  const uint32_t lane = threadIdx.x & 63;
+  mq_push(s, m, ca, a.p - qa, 2 * lane);
+  if (m.tail - m.head >= 64u) mq_process(s, P, m);
+  mq_push(s, m, cb, b.p - qb, 2 * lane + 1);
+  if (m.tail - m.head >= 64u) mq_process(s, P, m);
+}
+
+// the walk reads its result slot back (branch-free but for the exact length
+// of a match that reached nice_len, as the measurement's own update)
+__device__ __forceinline__ void mq_poll(Walk &w, const MatchShared *s, const DeflateParams &P, uint32_t slot) {
+  const uint32_t k = s->mr[threadIdx.x >> 6][slot];
+  uint32_t len = k >> 15;
+  const uint32_t dist = 0x7FFFu - (k & 0x7FFFu);
+  // (the slot's winner: longest key, then nearest; the carried match's own
+  // entry never wins; a walk that stopped at nice_len holds its exact length,
+  // which no key exceeds)
+  const bool upd = len > w.best_len;
+  if (upd && (int)len >= P.nice_len) len = mq_measure(s, w.p - dist, w.p, w.max_len);
+  const bool stop = upd && ((int)len >= P.nice_len || len >= w.max_len);
+  const bool newo = upd && !stop && len >= 4;
+  w.best_len = upd ? len : w.best_len;
+  w.best_dist = upd ? dist : w.best_dist;
+  w.active = w.active && !stop;
+  w.o = newo ? len - 3 : w.o;
+  w.omask = newo ? 0xFFFFFFFFu : w.omask;
+  const uint32_t npw = ld32(s, w.p + w.o);
+  w.pw = newo ? npw : w.pw;
+}
+
+// one pair loop of search_quad with queued measurement.  A wave-uniform
+// loop of at most mc steps (no walk takes more hops): the passes need every
+// lane, so no lane leaves before the wave's last walk ends; an inactive
+// walk's hops push nothing.  The slots start at the walks' carried matches
+// with the largest distance field, so that no candidate of equal length
+// replaces one (as the walk's strict > keeps it).
+__device__ __forceinline__ void mq_pair_loop(Walk &wa, Walk &wb, MatchShared *s, const DeflateParams &P, MqState &m,
+                                             int mc) {
+  const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  s->mr[wv][2 * lane] = wa.best_len >= 3 ? mq_key(wa.best_len, 0) : 0u;
+  s->mr[wv][2 * lane + 1] = wb.best_len >= 3 ? mq_key(wb.best_len, 0) : 0u;
+  m.head = m.tail = 0;
+  m.ready = false;
+  for (int step = 0; step < mc && __ballot(wa.active || wb.active) != 0; ++step) {
+    walk_pair_hop_mq(wa, wb, s, P, step, m);
+    // (every MQ_FLUSH + 1 steps the queue is measured even when short: long
+    // chains would otherwise walk on with an old filter)
+    if ((step & MQ_FLUSH) == MQ_FLUSH && m.tail != m.head) mq_process(s, P, m);
+    if (m.ready) {
+      mq_poll(wa, s, P, 2 * lane);
+      mq_poll(wb, s, P, 2 * lane + 1);
+      m.ready = false;
+    }
+  }
+  // (fewer than 64 are left: one pass; bounded all the same)
+  for (int k = 0; k < 2 && m.tail != m.head; ++k) mq_process(s, P, m);
+  mq_poll(wa, s, P, 2 * lane);
+  mq_poll(wb, s, P, 2 * lane + 1);
 }
 
 
@@ -1030,11 +1227,29 @@ __device__ __forceinline__ uint32_t walk_finish(const Walk &w, const MatchShared
 // (0, or a preset dictionary's first byte: near probes stop there, the chains
 // and the 4-byte table never held a position below it).  DICT = false: the
 // floor is 0 at compile time
-template <bool DICT>
-__device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32_t pb, uint32_t p0, uint32_t p1,
+// R = ROLE_PROBE adds the walks' counts to late and nmeas.  R = ROLE_QUEUED:
+// every lane of the wave stays (the queue's passes need the whole wave);
+// lanes past the sub-chunk walk nothing and store nothing.
+template <bool DICT, Role R>
+__device__ void search_quad(MatchShared *s, const DeflateParams &P, uint32_t pb, uint32_t p0, uint32_t p1,
                             uint32_t pml, uint32_t lim4, uint32_t floor, Key key, uint32_t *res_out, int mc,
-                            uint32_t &late) {
-  if (pb >= p1) return;
+                            [[maybe_unused]] uint32_t &late, [[maybe_unused]] uint32_t &nmeas) {
+  [[maybe_unused]] MqState m;
+  if constexpr (R == ROLE_QUEUED) {
+    m.pml = pml;
+    if (pb >= p1) pml = 0;  // (no walk of this lane starts: max_len 0)
+  } else {
+    if (pb >= p1) return;
+  }
+  // the pair loop of positions pb + k0 and pb + k0 + 2
+  auto pair_loop = [&](Walk &wa, Walk &wb, uint32_t k0) {
+    if constexpr (R == ROLE_QUEUED) {
+      m.pbase = pb - 4 * (threadIdx.x & 63) + k0;
+      mq_pair_loop(wa, wb, s, P, m, mc);
+    } else {
+      for (int step = 0; wa.active || wb.active; ++step) walk_pair_step<R>(wa, wb, s, P, step);
+    }
+  };
   // bytes [pb - 16, pb + 20) (pb is a multiple of 4; before rel 0 the words
   // are never used: near distances stay <= p)
   uint32_t w[9];
@@ -1053,9 +1268,10 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
   const uint32_t nr2 = near_any<2, 1>(w, win32<18>(w), ~0u), nr3 = near_any<3, 1>(w, win32<19>(w), ~0u);
   Walk wa, wb;
   wa.late = wb.late = 0;
+  wa.nmeas = wb.nmeas = 0;
   walk_init(wa, s, P, pb, pml, win32<16>(w), win32<20>(w), win32<24>(w), win32<28>(w), 0, 0, l8.x & 0xFFFFu, mc);
   walk_init(wb, s, P, pb + 2, pml, win32<18>(w), win32<22>(w), win32<26>(w), win32<30>(w), 0, 0, l8.y & 0xFFFFu, mc);
-  for (int step = 0; wa.active || wb.active; ++step) walk_pair_step(wa, wb, s, P, step);
+  pair_loop(wa, wb, 0);
   out[0] = walk_finish<0, DICT>(wa, s, P, w, nr0, lim4, l4.x & 0xFFFFu, floor, c0l, c0d);
   out[2] = walk_finish<2, DICT>(wb, s, P, w, nr2, lim4, l4.y & 0xFFFFu, floor, c2l, c2d);
 #ifdef ZT_DF_NOCARRY  // experiment: positions 1 and 3 start without the carried match
@@ -1063,8 +1279,11 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
 #endif
   walk_init(wa, s, P, pb + 1, pml, win32<17>(w), win32<21>(w), win32<25>(w), win32<29>(w), c0l, c0d, l8.x >> 16, mc);
   walk_init(wb, s, P, pb + 3, pml, win32<19>(w), win32<23>(w), win32<27>(w), win32<31>(w), c2l, c2d, l8.y >> 16, mc);
-  for (int step = 0; wa.active || wb.active; ++step) walk_pair_step(wa, wb, s, P, step);
-  late += wa.late + wb.late;
+  pair_loop(wa, wb, 1);
+  if constexpr (R == ROLE_PROBE) {
+    late += wa.late + wb.late;
+    nmeas += wa.nmeas + wb.nmeas;
+  }
   out[1] = walk_finish<1, DICT>(wa, s, P, w, nr1, lim4, l4.x >> 16, floor, cl, cd);
   out[3] = walk_finish<3, DICT>(wb, s, P, w, nr3, lim4, l4.y >> 16, floor, cl, cd);
   // the positions' own bytes (res_pack)
@@ -1072,6 +1291,9 @@ __device__ void search_quad(const MatchShared *s, const DeflateParams &P, uint32
   out[1] |= win32<17>(w) << 24;
   out[2] |= win32<18>(w) << 24;
   out[3] |= win32<19>(w) << 24;
+  if constexpr (R == ROLE_QUEUED) {
+    if (pb >= p1) return;
+  }
   if (pb + 4 <= p1) {
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
     u32x4 v = {out[0], out[1], out[2], out[3]};
@@ -1142,11 +1364,7 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
   key.kmask2 = P.klen >= 8 ? 0xFFFFFFFFu : P.klen == 6 ? 0xFFFFu : P.klen == 5 ? 0xFFu : 0u;
   const uint32_t kext = (uint32_t)P.klen - 1;  // a key at p needs bytes up to p + kext
 
-#ifdef ZT_DF_HEAD16
   for (uint32_t i = t; i < DF_HSIZE / 2; i += DF_THREADS) s.head[i] = 0x80008000u;  // (rel 0 - 32768: out of reach)
-#else
-  for (uint32_t i = t; i < DF_HSIZE; i += DF_THREADS) s.head[i] = kNoHead;
-#endif
   for (uint32_t i = t; i < DF_H4SIZE; i += DF_THREADS) s.head4[i] = kNoHead;
   // the last kext positions of the first sub-chunk read link4 before any
   // link reached their slots: no candidate (not the LDS left by an earlier
@@ -1183,11 +1401,15 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
       s.linked = link ? inserted : ih;
       s.linked4 = link ? inserted : ih;
       s.work = 0;
-      if (p0 > rs && ((p0 - rs) % DF_BLOCK) == DF_SUB)  // (the probe's counts are complete: a barrier since)
+      if (p0 > rs && ((p0 - rs) % DF_BLOCK) == DF_SUB) {  // (the probe's counts are complete: a barrier since)
         s.depth = P.adapt_depth && s.late * 4096u <= (uint32_t)P.adapt_thr * DF_SUB     ? P.adapt_depth
                   : P.adapt_depth2 && s.late2 * 4096u <= (uint32_t)P.adapt_thr2 * DF_SUB ? P.adapt_depth2
                                                                                           : P.max_chain;
-      if (probe_sub) s.late = s.late2 = 0;
+        // (both ways of measuring give the same matches: the choice is one of time only)
+        s.queued = P.mq_thr && (uint64_t)s.nmeas * 4096u >= (uint64_t)P.mq_thr * DF_SUB;
+        atomicAdd(&g_match_modes[s.queued ? 0 : 1], 1ull);
+      }
+      if (probe_sub) s.late = s.late2 = s.nmeas = 0;
     }
     // the next sub-chunk is fetched while this one is searched
     const uint32_t n0 = p0 + DF_SUB;
@@ -1206,9 +1428,7 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
       pml = bend < dend ? bend : dend;
     }
     if (link) hash_keys(&s, inserted, ih, key);
-#ifdef ZT_DF_HEAD16
     if ((p0 / DF_SUB) % HEAD_SWEEP == 0 && link) head_sweep(&s, p0);
-#endif
     lds_barrier();
     DF_T(t1);
     // wave 0 links the 8-byte-key chains and wave 1 the 4-byte-key table,
@@ -1234,7 +1454,10 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
     if (p0 >= rs) {
       const uint32_t nss = (p1 - p0 + 255) / 256;
       const int mc = probe_sub || !P.adapt_depth ? P.max_chain : s.depth;
-      uint32_t late = 0;
+      uint32_t late = 0, nmeas = 0;
+      // (workgroup-uniform, fixed for the sub-chunk)
+      const bool counting = P.adapt_depth || P.mq_thr;
+      const Role role = probe_sub ? (counting ? ROLE_PROBE : ROLE_PLAIN) : counting && s.queued ? ROLE_QUEUED : ROLE_PLAIN;
       uint32_t *res_out = P.res + (h_lo + p0 - P.halo);  // res[input pos]: rel r <-> input h_lo + r - halo
       for (;;) {
         uint32_t ss = 0;
@@ -1252,8 +1475,13 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
 #ifdef ZT_DF_TIME
         DF_T(w1);
 #endif
-        search_quad<DICT>(&s, P, p0 + 256 * ss + 4 * (t & 63), p0, p1, pml, ih, DICT ? floor : 0u, key, res_out, mc,
-                          late);
+        const uint32_t pb = p0 + 256 * ss + 4 * (t & 63);
+        if (role == ROLE_PROBE)
+          search_quad<DICT, ROLE_PROBE>(&s, P, pb, p0, p1, pml, ih, DICT ? floor : 0u, key, res_out, mc, late, nmeas);
+        else if (role == ROLE_QUEUED)
+          search_quad<DICT, ROLE_QUEUED>(&s, P, pb, p0, p1, pml, ih, DICT ? floor : 0u, key, res_out, mc, late, nmeas);
+        else
+          search_quad<DICT, ROLE_PLAIN>(&s, P, pb, p0, p1, pml, ih, DICT ? floor : 0u, key, res_out, mc, late, nmeas);
 #ifdef ZT_DF_TIME
         DF_T(w2);
         t_wait += w1 - w0;
@@ -1266,6 +1494,10 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
         for (int o = 32; o; o >>= 1) late += (uint32_t)__shfl_xor((int)late, o, 64);
         if ((t & 63) == 0 && (late & 0xFFFFu)) atomicAdd(&s.late, late & 0xFFFFu);
         if ((t & 63) == 0 && (late >> 16)) atomicAdd(&s.late2, late >> 16);
+      }
+      if (probe_sub && P.mq_thr) {
+        for (int o = 32; o; o >>= 1) nmeas += (uint32_t)__shfl_xor((int)nmeas, o, 64);
+        if ((t & 63) == 0 && nmeas) atomicAdd(&s.nmeas, nmeas);
       }
     }
     DF_T(t2);
@@ -2750,6 +2982,7 @@ __global__ __launch_bounds__(256) void stored_blocks(const uint8_t *__restrict__
 struct DeflateLevel {
   int max_chain, nice, lazy, too_far, skip, klen, probe, good, opt;
   int adapt_depth = 0, adapt_thr = 0, adapt_depth2 = 0, adapt_thr2 = 0;  // per-block depth (DeflateParams)
+  int mq_thr = 0;  // per-block queued measurement (DeflateParams; 0: never)
 };
 
 static DeflateLevel level_params_base(int level);
@@ -2766,6 +2999,15 @@ static DeflateLevel level_params(int level) {
     L.adapt_thr = 40;
     L.adapt_depth2 = 10;
     L.adapt_thr2 = 320;
+    // queued measurement where the probe measured a candidate at every
+    // second position or more: wordsalad's blocks (97 %) and part of
+    // source text's, none of structured data's (0.002 per position).  Match ms
+    // per GiB with the threshold 0 / 256 / 1024 / 2048 / 3072: wordsalad 45.3
+    // / 40.0 / 39.9 / 40.0 / 39.9, source text 44.4 / 43.7 / 43.4 / 43.1 /
+    // 44.4, structured 16.3-16.4 throughout; 1 (every block that measured
+    // anything) costs structured 11 %.  Off at the other levels: level 9's
+    // long walks lose 40 % with it, level 1's 20 % (tools/experiments/README.md)
+    L.mq_thr = 2048;
   }
   // tuning hook: ZT_DF_ADAPT="depth,thr[,depth2,thr2]" (per-block depth; depth 0: off)
   if (const char *e = getenv("ZT_DF_ADAPT")) {
@@ -2777,6 +3019,10 @@ static DeflateLevel level_params(int level) {
       L.adapt_thr2 = t2;
     }
   }
+  // tuning hook: ZT_DF_MQ=<n>: blocks whose probe measured at least n
+  // candidates per 4096 positions measure through the queues (0: none, 1:
+  // every block whose probe measured anything); the streams do not depend on it
+  if (const char *e = getenv("ZT_DF_MQ")) L.mq_thr = atoi(e) > 0 ? atoi(e) : 0;
   return L;
 }
 static DeflateLevel level_params_base(int level) {
@@ -2938,6 +3184,7 @@ int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, in
   P.adapt_thr = L.adapt_thr;
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
+  P.mq_thr = L.mq_thr;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   P.span = nullptr;
@@ -3061,6 +3308,7 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   P.adapt_thr = L.adapt_thr;
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
+  P.mq_thr = L.mq_thr;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   P.span = d_span;
@@ -3126,6 +3374,18 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   ZT_TRY(timing_collect(c, &c->times.deflate_pipeline_ms, &c->times.deflate_pipelines, 1));
   for (size_t f = 0; f < count; ++f) out_off[f] = boff[first[f]];
   out_off[count] = boff[G.nblocks];
+  return ZT_OK;
+}
+
+// blocks that measured through the queues, blocks that measured at once,
+// since the last call (of the current device)
+extern "C" int zt_debug_match_modes(uint64_t out[2]) {
+  unsigned long long v[2] = {}, z[2] = {};
+  ZT_HIP(hipDeviceSynchronize());
+  ZT_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_match_modes), sizeof v));
+  ZT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_match_modes), z, sizeof z));
+  out[0] = v[0];
+  out[1] = v[1];
   return ZT_OK;
 }
 

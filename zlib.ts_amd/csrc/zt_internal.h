@@ -222,6 +222,10 @@ int checksums_batch_dev(DeviceCtx *c, const uint8_t *frame, size_t count, const 
 void gzip_header(const zt_gzip_opts *opts, std::vector<uint8_t> &hd);  // container_api.cpp
 int current_device();                                                 // zt_api.cpp (this thread's)
 std::vector<int> batch_devices();                                     // zt_set_devices, else {current}
+// debug (deflate.hip; exported, not part of include/zt.h): blocks of the
+// match kernel that measured their candidates through the queues (out[0]) and
+// at once (out[1]) since the last call; reads and clears the device counter
+extern "C" int zt_debug_match_modes(uint64_t out[2]);
 // batch deflate (deflate.hip): streams packed at 32 KiB boundaries, one pipeline
 size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded);
 // a preset dictionary as the match kernel reads it (dict_host.h: dict_layout):

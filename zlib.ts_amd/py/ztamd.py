@@ -137,6 +137,8 @@ def _load():
         "zt_timing_read": ([P(KernelTimes)], ctypes.c_int),
         "zt_scratch_bytes": ([P(sz), P(sz)], ctypes.c_int),
         "zt_release_scratch": ([], ctypes.c_int),
+        # debug (csrc/zt_internal.h)
+        "zt_debug_match_modes": ([P(ctypes.c_uint64)], ctypes.c_int),
         # include/zt_zipcrypto.h
         "zt_zipcrypto_encrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
         "zt_zipcrypto_decrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
@@ -737,6 +739,14 @@ def timing_read():
             "inflate_tok_ms": t.inflate_tok_ms, "inflate_toks": t.inflate_toks,
             "inflate_paths": list(t.inflate_paths), "general_passes": t.general_passes,
             "blocks_unsearched": t.blocks_unsearched}
+
+
+def debug_match_modes():
+    """(queued, at once): blocks of the deflate match kernel by the way they measured
+    their candidates, since the last call (reads and clears the device counter)."""
+    v = (ctypes.c_uint64 * 2)()
+    _check(lib.zt_debug_match_modes(v))
+    return int(v[0]), int(v[1])
 
 
 def scratch_bytes():
