@@ -25,8 +25,9 @@
 //      backward shortest-path DP over every position (cut lengths 3..16 and
 //      the full match), choices written over res.
 //   3. parse_kernel -- one wave per block: parse of the DP's choices
-//      (LDS-DMA staged, pointer doubling), tokens over res, histograms (a
-//      small LDS footprint: many waves per CU).
+//      (lane-parallel: 64 lanes x 32 positions per step, the lanes' entries
+//      settled by pointer jumping), tokens over res, histograms (a small
+//      LDS footprint: many waves per CU).
 //      block_kernel -- one wave per block: length-limited Huffman lengths by
 //      wave-parallel package-merge, canonical codes, the RLE'd code-length
 //      header, and the smallest of stored / fixed / dynamic.
@@ -162,6 +163,10 @@ struct DeflateParams {
   // rest of the block measures through the waves' queues (mq_pair_loop): the
   // same matches, found with fuller waves
   int mq_thr;
+  // 1: parse_kernel and price_kernel walk the path window by window
+  // (parse_block_regs) instead of lane-parallel (ZT_PARSE_SERIAL; the streams
+  // do not depend on it)
+  int parse_serial;
   // batch of independent streams (zt_deflate_batch_dev): stream f occupies
   // whole blocks from a 32 KiB-aligned offset; per block the [start, end) of
   // its stream (relative to halo = 0), or null for one stream of n bytes
@@ -1547,15 +1552,15 @@ struct HufScratch {
   uint32_t bl_count[16];
 };
 
-// parse staging ring (parse_block_dma)
-constexpr int PB_CH = 4;
-#ifndef ZT_PB_NCH
-#define ZT_PB_NCH 4
-#endif
-constexpr int PB_NCH = ZT_PB_NCH;
-constexpr int PB_LOADS = PB_CH;  // global_load_lds per chunk (res words; the bytes ride in res)
-struct ParseStage {
-  uint32_t res[PB_NCH][PB_CH * 64];
+// lane-parallel parse (parse_block_lanes): a step is 64 lanes x PL_LANE
+// positions, each lane's res words staged in an LDS row of its own
+constexpr int PL_LANE = 32;            // positions per lane: one 128-byte line of res
+constexpr int PL_STEP = 64 * PL_LANE;  // positions per step
+// dwords per row, odd: word j of the 64 rows falls in 32 distinct banks per half-wave
+constexpr int PL_ROW = PL_LANE + 1;
+struct LaneStage {
+  uint32_t row[64][PL_ROW];  // res words of the step, the length after the lazy rule
+  uint8_t ent[64];           // entry offset handed to a lane by the on-path lane that jumps into it
 };
 
 struct BlockShared {
@@ -1789,11 +1794,9 @@ __device__ __forceinline__ uint32_t fixed_lit(uint32_t sym) {
 }
 
 
-// LDS histogram increment as inline asm: the compiler puts an
-// s_waitcnt vmcnt(0) before every LDS store it sees while LDS-DMA loads are in
-// flight (it cannot tell the parse ring from the histograms), which would
-// drain parse_block_dma's prefetch at every window.  (LDS operations complete
-// in order, so the compiler's own lgkmcnt waits stay sufficient.)
+// LDS histogram increment as inline asm: one ds_add_u32 without a returned
+// value.  (LDS operations complete in order, so the compiler's own lgkmcnt
+// waits stay sufficient.)
 __device__ __forceinline__ void lds_inc(uint32_t *p) {
   const uint32_t a = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)p;
   __asm__ volatile("ds_add_u32 %0, %1" ::"v"(a), "v"(1u) : "memory");
@@ -1917,56 +1920,236 @@ __device__ uint32_t parse_block_regs(S *s, const DeflateParams &P, uint32_t *r_b
   return ntok;
 }
 
-// LDS-DMA driver for whole, 4-byte aligned blocks: chunks of PB_CH windows
-// (res words and data bytes) stream into a ring of PB_NCH chunks by
-// global_load_lds, PB_NCH - 1 chunks ahead, with one counted vmcnt wait per
-// chunk -- the register driver's loads could not stay in flight across the
-// window loop's branches (the compiler waited for each window's loads).
-__device__ __forceinline__ void vm_wait_loads(void) {
-  // vmcnt(PB_LOADS * (PB_NCH - 2)): chunks c and c + 1 have landed (loads
-  // complete in order; stores in between only make this wait longer)
-  constexpr int N = PB_LOADS * (PB_NCH - 2);
-  static_assert(N < 64, "vmcnt field");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
-template <bool WRITE, class S>
-__device__ uint32_t parse_block_dma(S *s, ParseStage *st, const DeflateParams &P, uint32_t *r_blk, uint32_t len) {
-  const int lane = threadIdx.x & 63;
-  const uint32_t nch = len / (PB_CH * 64);  // len: a multiple of PB_CH * 64
-  auto issue = [&](uint32_t c) {
-    // past the block: re-read chunk 0 (the count of loads stays fixed)
-    const uint32_t cc = c < nch ? c : 0u;
-    const uint32_t slot = c % PB_NCH;
-#pragma unroll
-    for (int w = 0; w < PB_CH; ++w)
-      __builtin_amdgcn_global_load_lds(r_blk + cc * (PB_CH * 64) + w * 64 + lane, &st->res[slot][w * 64], 4, 0, 0);
-  };
-#pragma unroll
-  for (int c = 0; c < PB_NCH - 1; ++c) issue((uint32_t)c);
-  uint32_t entry = 0, ntok = 0;
-  for (uint32_t c = 0; c < nch; ++c) {
-    issue(c + PB_NCH - 1);
-    vm_wait_loads();
-    const uint32_t slot = c % PB_NCH, nslot = (c + 1) % PB_NCH;
-    for (int w = 0; w < PB_CH; ++w) {
-      const uint32_t w0 = c * (PB_CH * 64) + (uint32_t)w * 64;
-      if (entry >= 64) {
-        entry -= 64;
-        continue;
-      }
-      const uint32_t r = st->res[slot][w * 64 + lane];
-      const uint32_t r_next = w + 1 < PB_CH ? st->res[slot][(w + 1) * 64] : st->res[nslot][0];
-      parse_window<WRITE>(s, P, r_blk, len, w0, r, r_next, entry, ntok);
+// ---- lane-parallel driver -------------------------------------------------
+// The choice at every position is fixed before the parse (the match, the lazy
+// rule or the DP's length), so the walk only finds which positions lie on the
+// path from the start: list ranking.  A step covers PL_STEP positions, lane k
+// the PL_LANE positions from 32 k on, held as one row of LDS words.
+//
+// The path through one lane's positions from offset e: literal runs by mask
+// arithmetic on the match mask mm, one length lookup per match on the path.
+// `old` is the path of an earlier walk of the lane (0: none): once the walk
+// reaches one of its positions, the rest of the path and the exit ex (>=
+// PL_LANE, relative to the lane) are that walk's.
+__device__ __forceinline__ void lane_walk(const uint32_t *row, uint32_t mm, uint32_t e, uint32_t old, uint32_t &path,
+                                          uint32_t &ex) {
+  uint32_t p = 0, cur = e;
+  bool merged = false;
+  while (cur < (uint32_t)PL_LANE) {
+    const uint32_t from = ~0u << cur;
+    const uint32_t rest = mm & from;
+    const uint32_t m = rest ? (uint32_t)__builtin_ctz(rest) : 32u;  // next match, or the end
+    const uint32_t below = m >= 32 ? ~0u : (1u << m) - 1;
+    const uint32_t upto = m >= 31 ? ~0u : (2u << m) - 1;
+    if (old & from & upto) {
+      p |= (below | old) & from;
+      merged = true;
+      break;
+    }
+    p |= below & from;
+    cur = m;
+    if (m < 32) {
+      p |= 1u << m;
+      cur = m + res_len(row[m]);
     }
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): no DMA into the ring after return
-  return ntok;
+  path = p;
+  if (!merged) ex = cur;
 }
 
-template <bool WRITE, class S>
-__device__ uint32_t parse_block(S *s, ParseStage *st, const DeflateParams &P, uint32_t *r_blk, uint32_t len) {
-  if (len % (PB_CH * 64) == 0 && len > 0) return parse_block_dma<WRITE>(s, st, P, r_blk, len);
-  return parse_block_regs<WRITE>(s, P, r_blk, len);
+typedef unsigned int pl_u32x4 __attribute__((ext_vector_type(4)));
+
+// The lane's words w (sequence positions pos0 ..) into its row, branch-free
+// and statically unrolled; returns the mask of match positions.  LZ: the
+// one-step lazy rule as in parse_window (a longer match at i + 1 < slen defers
+// the one at i: its length field is cleared); nbw is the word after the
+// lane's last.
+template <bool LZ>
+__device__ __forceinline__ uint32_t lane_facts(uint32_t *row, const pl_u32x4 (&w)[PL_LANE / 4], uint32_t nbw,
+                                               uint32_t pos0, uint32_t slen) {
+  uint32_t mm = 0;
+#pragma unroll
+  for (int j = 0; j < PL_LANE; ++j) {
+    uint32_t r = w[j >> 2][j & 3];
+    uint32_t L = res_len(r);
+    if (LZ) {
+      const uint32_t nb = res_len(j + 1 < PL_LANE ? w[((j + 1) & 31) >> 2][(j + 1) & 3] : nbw);
+      const bool defer = (L >= 3) & (nb > L) & (pos0 + (uint32_t)j + 1 < slen);
+      r = defer ? r & ~(511u << 15) : r;
+      L = defer ? 0u : L;
+    }
+    mm |= (L >= 3 ? 1u : 0u) << j;
+    row[j] = r;
+  }
+  return mm;
+}
+
+// One sequence of len positions at r_blk (PIECE = 0), or npieces sequences of
+// PIECE positions each, `stride` words apart, every one walked from its own
+// start with nothing carried between them (PIECE / PL_LANE lanes per piece,
+// as many pieces per step as fill the wave).  Per step:
+//  1. every lane loads its line of res (the next step's is prefetched), applies
+//     the lazy rule, builds its match mask and stages the words in its row;
+//  2. every lane walks its positions from offset 0 (the sequence's first lane
+//     from the carried entry): a speculative path and exit;
+//  3. the exits link the lanes into lists; pointer jumping finds the lanes on
+//     the list from the sequence's entry lane, each on-path lane hands its
+//     successor the offset it enters at, and a lane whose walk assumed another
+//     offset walks again (lane_walk joins its earlier path where they meet).
+//     Repeated until no on-path lane changed: every round settles at least the
+//     leftmost unsettled on-path lane, so at most 64 rounds for any data;
+//  4. on-path lanes emit their tokens in position order (a wave prefix sum of
+//     the per-lane counts places them) and count the histograms.
+// In place: after step t, ntok <= PL_STEP (t + 1), so a step's stores end at or
+// before the end of its own positions; its words are in LDS by then (the
+// stores depend on them), the prefetched next step lies wholly beyond, and
+// later steps are loaded only after these stores.
+// (WRITE = false: histograms only, res untouched)
+template <bool WRITE, int PIECE, class S>
+__device__ uint32_t parse_block_lanes(S *s, const DeflateParams &P, uint32_t *r_blk, uint32_t len, uint32_t npieces,
+                                      uint32_t stride) {
+  static_assert(PIECE % PL_LANE == 0 && (PIECE == 0 || PL_STEP % PIECE == 0), "pieces are whole lanes, steps whole pieces");
+  constexpr uint32_t LP = PIECE ? PIECE / PL_LANE : 64;  // lanes per sequence in a step
+  constexpr uint32_t PS = 64 / LP;                       // sequences per step
+  const uint32_t lane = threadIdx.x & 63;
+  LaneStage *st = &s->stage;
+  uint32_t *row = st->row[lane];
+  const bool lz = P.lazy && !P.opt;
+  const uint32_t nsteps = PIECE ? (npieces + PS - 1) / PS : (len + PL_STEP - 1) / PL_STEP;
+  const uint32_t sl = lane & (LP - 1);  // lane within its sequence's lanes
+  // the lane's line in step t: position within its sequence, that sequence's
+  // length (0: none) and the words
+  auto seq_pos = [&](uint32_t t) -> uint32_t { return PIECE ? sl * PL_LANE : t * PL_STEP + lane * PL_LANE; };
+  auto seq_len = [&](uint32_t t) -> uint32_t {
+    if (!PIECE) return t < nsteps ? len : 0u;
+    return t * PS + lane / LP < npieces ? (uint32_t)PIECE : 0u;
+  };
+  auto load = [&](uint32_t t, pl_u32x4 *w) {
+    const uint32_t *src = PIECE ? r_blk + (size_t)(t * PS + lane / LP) * stride + sl * PL_LANE
+                                : r_blk + t * PL_STEP + lane * PL_LANE;
+    const bool in = seq_pos(t) < seq_len(t);
+#pragma unroll
+    for (int q = 0; q < PL_LANE / 4; ++q)
+      w[q] = in ? reinterpret_cast<const pl_u32x4 *>(src)[q] : pl_u32x4{0u, 0u, 0u, 0u};
+  };
+  uint32_t entry = 0;  // first path position of the sequence not yet walked (PIECE = 0)
+  uint32_t ntok = 0;
+  pl_u32x4 nw[PL_LANE / 4];
+  load(0, nw);
+  for (uint32_t t = 0; t < nsteps; ++t) {
+    pl_u32x4 cw[PL_LANE / 4];
+#pragma unroll
+    for (int q = 0; q < PL_LANE / 4; ++q) cw[q] = nw[q];
+    load(t + 1, nw);
+    const uint32_t pos0 = seq_pos(t), slen = seq_len(t);
+    const uint32_t nvalid = pos0 < slen ? (slen - pos0 < (uint32_t)PL_LANE ? slen - pos0 : (uint32_t)PL_LANE) : 0u;
+    const uint32_t vm = nvalid >= 32 ? ~0u : (1u << nvalid) - 1;
+    // 1. lazy rule, match mask, rows.  The neighbour of the lane's last
+    // position is the next lane's first word, lane 63's the next step's
+    uint32_t nbw = 0;
+    if (lz) {
+      nbw = (uint32_t)__shfl_down((int)cw[0][0], 1, 64);
+      const uint32_t first_next = (uint32_t)__shfl((int)nw[0][0], 0, 64);
+      if (lane == 63) nbw = first_next;
+    }
+    // (one wave-uniform branch on the lazy rule around the 32 unrolled
+    // positions: tested per position it cost an exec-mask branch each, 700
+    // instructions per step for this part)
+    const uint32_t mm = (lz ? lane_facts<true>(row, cw, nbw, pos0, slen) : lane_facts<false>(row, cw, nbw, pos0, slen)) & vm;
+    // 2. speculative walk
+    uint32_t src, soff, send;  // the sequence's entry lane and offset; the end of its lanes in this step
+    if (PIECE) {
+      src = lane & ~(LP - 1);
+      soff = 0;
+      send = (uint32_t)PIECE;
+    } else {
+      const uint32_t rel = entry - t * PL_STEP;  // < PL_STEP: a match is at most 258 long
+      src = rel / PL_LANE;
+      soff = rel % PL_LANE;
+      send = (t + 1) * PL_STEP;
+    }
+    uint32_t a = lane == src ? soff : 0u;  // the offset the lane's walk assumed
+    uint32_t path = 0, ex = PL_LANE;
+    lane_walk(row, mm, a, 0u, path, ex);
+    path &= vm;
+    // 3. entries across lanes
+    bool on = false;
+    uint32_t nxt = 64;
+    for (int round = 0; round <= 64; ++round) {  // (settled after at most 64; the bound is never the exit)
+      nxt = pos0 + ex < send ? lane + ex / PL_LANE : 64u;  // the lane the exit lies in
+      if (__ballot(nxt != lane + 1 && sl != LP - 1) == 0) {
+        // every exit lies in the next lane (a sequence's last lane has none):
+        // the lists are the sequences' lanes from their entry lane on
+        on = lane >= src;
+      } else {
+        uint32_t ptr = nxt;
+        uint64_t reach = 1ull << lane;
+        for (int rnd = 0; rnd < 6 && __ballot(ptr < 64); ++rnd) {
+          const bool in = ptr < 64;
+          const int from = in ? (int)ptr : (int)lane;
+          const uint32_t rlo = (uint32_t)__shfl((int)(uint32_t)reach, from, 64);
+          const uint32_t rhi = (uint32_t)__shfl((int)(uint32_t)(reach >> 32), from, 64);
+          const uint32_t nptr = (uint32_t)__shfl((int)ptr, from, 64);
+          if (in) {
+            reach |= ((uint64_t)rhi << 32) | rlo;
+            ptr = nptr;
+          }
+        }
+        const uint32_t slo = (uint32_t)__shfl((int)(uint32_t)reach, (int)src, 64);
+        const uint32_t shi = (uint32_t)__shfl((int)(uint32_t)(reach >> 32), (int)src, 64);
+        on = (((((uint64_t)shi << 32) | slo) >> lane) & 1) != 0;
+      }
+      if (on && nxt < 64) st->ent[nxt] = (uint8_t)(ex % PL_LANE);
+      wsync();
+      const uint32_t te = lane == src ? soff : (uint32_t)st->ent[lane];
+      const bool changed = on && te != a;
+      wsync();
+      if (!__ballot(changed)) break;
+      bool moved = false;  // the walk left the lane elsewhere than before
+      if (changed) {
+        const uint32_t ex0 = ex;
+        lane_walk(row, mm, te, path, path, ex);
+        path &= vm;
+        a = te;
+        moved = ex != ex0;
+      }
+      // no exit moved: the lists, and so every entry, stay as they are
+      if (!__ballot(moved)) break;
+    }
+    if (!on) path = 0;
+    if (!PIECE) {
+      // the one on-path lane whose exit leaves the step carries the entry on
+      const uint64_t last = __ballot(on && nxt >= 64);
+      const int ll = last ? __builtin_ctzll(last) : 0;
+      entry = (uint32_t)__builtin_amdgcn_readlane((int)(pos0 + ex), ll);
+    }
+    // 4. tokens and histograms
+    const uint32_t cnt = (uint32_t)__popc(path);
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint32_t v = (uint32_t)__shfl_up((int)incl, off, 64);
+      if (lane >= (uint32_t)off) incl += v;
+    }
+    // (each lane stores its own tokens at its running offset; compacted in the
+    // rows and copied out 64 in a row instead: parse 1.211 -> 1.189 ms, not
+    // kept, tools/experiments/parse_lanes_staged_stores.patch)
+    uint32_t idx = ntok + incl - cnt;
+    for (uint32_t q = path; q; q &= q - 1) {
+      const uint32_t r = row[__builtin_ctz(q)];
+      const uint32_t L = res_len(r);
+      const bool mt = L >= 3;
+      const uint32_t token = mt ? (L << 16) | res_dist(r) : res_byte(r);
+      lds_inc(&s->lit_hist[mt ? 257 + len_sym(L) : token]);
+      if (mt) {
+        uint32_t eb, ev;
+        lds_inc(&s->dist_hist[dist_sym(res_dist(r), eb, ev)]);
+      }
+      if (WRITE) r_blk[idx++] = token;
+    }
+    ntok += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  }
+  return ntok;
 }
 
 // ================================ 1b. optparse_kernel ================================
@@ -2025,7 +2208,7 @@ struct BlockPrices {
 struct PriceShared {
   uint32_t lit_hist[288];
   uint32_t dist_hist[32];
-  ParseStage stage;
+  LaneStage stage;
 };
 
 __device__ __forceinline__ uint32_t op_price(uint32_t f, float inv_total) {
@@ -2068,11 +2251,17 @@ __global__ __launch_bounds__(64) void price_kernel(DeflateParams P) {
     // the sample in ZT_PRICE_PIECES pieces spread over the block, each parsed
     // greedily from its own start
     constexpr uint32_t pl = DF_BLOCK / ZT_PRICE_SAMPLE / ZT_PRICE_PIECES;
-    static_assert(pl % (PB_CH * 64) == 0, "pieces take the LDS-DMA driver");
-    for (int j = 0; j < ZT_PRICE_PIECES; ++j)
-      parse_block<false>(s, &s->stage, P, P.res + lo + (uint64_t)j * (DF_BLOCK / ZT_PRICE_PIECES), pl);
+    if (P.parse_serial) {
+      for (int j = 0; j < ZT_PRICE_PIECES; ++j)
+        parse_block_regs<false>(s, P, P.res + lo + (uint64_t)j * (DF_BLOCK / ZT_PRICE_PIECES), pl);
+    } else {
+      // PL_STEP / pl pieces per step, pl / PL_LANE lanes each
+      parse_block_lanes<false, (int)pl>(s, P, P.res + lo, 0u, ZT_PRICE_PIECES, DF_BLOCK / ZT_PRICE_PIECES);
+    }
+  } else if (P.parse_serial) {
+    parse_block_regs<false>(s, P, P.res + lo, plen);
   } else {
-    parse_block<false>(s, &s->stage, P, P.res + lo, plen);
+    parse_block_lanes<false, 0>(s, P, P.res + lo, plen, 0u, 0u);
   }
   wsync();
   BlockPrices *bp = reinterpret_cast<BlockPrices *>(P.slots + (size_t)blk * DF_SLOT);
@@ -2245,8 +2434,9 @@ __global__ __launch_bounds__(64, ZT_OP_MINW) void optparse_kernel(DeflateParams 
 // token count handed to block_kernel through the start of the block's slot
 // (its prices are consumed by then; block_kernel writes the header there only
 // after reading them).  A kernel of its own so that its LDS (histograms + the
-// LDS-DMA staging ring, 7.5 KiB) keeps 20 waves per CU on this latency-bound
-// walk, instead of block_kernel's 15 (its Huffman scratch, 10.3 KiB).
+// lane rows, 9.6 KiB) keeps 16 waves per CU, instead of block_kernel's 15
+// (its Huffman scratch, 10.3 KiB).  P.parse_serial (ZT_PARSE_SERIAL=1) takes
+// the serial window walk instead: the same tokens and histograms.
 __global__ __launch_bounds__(64) void parse_kernel(DeflateParams P) {
   __shared__ PriceShared sh;
   PriceShared *s = &sh;
@@ -2259,7 +2449,8 @@ __global__ __launch_bounds__(64) void parse_kernel(DeflateParams P) {
   for (int i = lane; i < 288; i += 64) s->lit_hist[i] = 0;
   if (lane < 32) s->dist_hist[lane] = 0;
   wsync();
-  const uint32_t ntok = parse_block<true>(s, &s->stage, P, P.res + lo, blen);
+  const uint32_t ntok = P.parse_serial ? parse_block_regs<true>(s, P, P.res + lo, blen)
+                                       : parse_block_lanes<true, 0>(s, P, P.res + lo, blen, 0u, 0u);
   wsync();
   uint32_t *hs = reinterpret_cast<uint32_t *>(P.slots + (size_t)blk * DF_SLOT);
   for (int i = lane; i < 288; i += 64) hs[i] = s->lit_hist[i];
@@ -2983,6 +3174,7 @@ struct DeflateLevel {
   int max_chain, nice, lazy, too_far, skip, klen, probe, good, opt;
   int adapt_depth = 0, adapt_thr = 0, adapt_depth2 = 0, adapt_thr2 = 0;  // per-block depth (DeflateParams)
   int mq_thr = 0;  // per-block queued measurement (DeflateParams; 0: never)
+  int parse_serial = 0;  // the serial window walk in parse / price (DeflateParams)
 };
 
 static DeflateLevel level_params_base(int level);
@@ -3023,6 +3215,10 @@ static DeflateLevel level_params(int level) {
   // candidates per 4096 positions measure through the queues (0: none, 1:
   // every block whose probe measured anything); the streams do not depend on it
   if (const char *e = getenv("ZT_DF_MQ")) L.mq_thr = atoi(e) > 0 ? atoi(e) : 0;
+  // A/B and test hook: ZT_PARSE_SERIAL=1: the serial window walk in
+  // parse_kernel and price_kernel (the reference the lane-parallel walk is
+  // tested against); the streams do not depend on it
+  if (const char *e = getenv("ZT_PARSE_SERIAL")) L.parse_serial = atoi(e) != 0;
   return L;
 }
 static DeflateLevel level_params_base(int level) {
@@ -3185,6 +3381,7 @@ int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, in
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
   P.mq_thr = L.mq_thr;
+  P.parse_serial = L.parse_serial;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   P.span = nullptr;
@@ -3309,6 +3506,7 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
   P.mq_thr = L.mq_thr;
+  P.parse_serial = L.parse_serial;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   P.span = d_span;
