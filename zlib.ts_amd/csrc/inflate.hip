@@ -324,7 +324,7 @@ __device__ __forceinline__ void inflate_stream(const InfJob &job, InfResult &res
         continue;
       }
       if (sym == 256) break;
-      const uint32_t ls = uni((uint32_t)(sym - 257));  // 286/287 decode as length 258, like the reference
+      const uint32_t ls = uni((uint32_t)(sym - 257));  // (<= 28: decode_sym rejects 286 / 287)
       uint32_t length = len_base(ls);
       const uint32_t lx = len_extra(ls);
       if (lx) {

@@ -373,7 +373,10 @@ int inflate_dev_member(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
       // the window cut a stream with sync points short (2): grow it, no
       // general-path attempt (it cannot finish inside the window either)
       if (seg == 2 && ne < n) continue;
-      if (seg >= 1) seg = inflate_general_dev(c, d_in, ne, index, &d_out, 0, &ol, &eip, s);
+      if (seg >= 1) {
+        d_out = nullptr;  // (the sync-point path may have placed an output of its own before it gave up)
+        seg = inflate_general_dev(c, d_in, ne, index, &d_out, 0, &ol, &eip, s);
+      }
       if (seg < 0) return seg;
       if (seg == 0) {
         uint8_t *h = host_out(ol);
@@ -551,7 +554,13 @@ int zt_inflate_raw(const uint8_t *in, size_t n, size_t index, const zt_inflate_o
     size_t ol = 0, eip = 0;
     int seg = inflate_segments_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
     // no sync points: speculative parallel decode at arbitrary bit offsets
-    if (seg >= 1) seg = inflate_general_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
+    if (seg >= 1) {
+      // (the sync-point path may have placed an output of its own before it gave up -- a
+      // status found while resolving, a match reaching behind a restart point: with that
+      // pointer and no capacity the general path would refuse the stream)
+      d_out = nullptr;
+      seg = inflate_general_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
+    }
     if (seg < 0) return seg;
     if (seg == 0) {
       uint8_t *h = host_out(ol, true);

@@ -30,7 +30,7 @@ constexpr int PRI = ZT_PRI;
 // symbols < 30).
 struct HuffTab {
   uint32_t pri[1 << PRI];
-  uint16_t sorted[320];
+  int16_t sorted[320];   // (signed: read_tables plants -1 where the fixed code's 286 / 287 are looked up)
   uint32_t first[16];
   uint32_t count[16];
   uint32_t offs[16];
@@ -57,9 +57,20 @@ __device__ __forceinline__ void wave_sync() {
 
 __device__ __forceinline__ uint64_t lanemask_lt(int lane) { return (lane == 0) ? 0ull : (~0ull >> (64 - lane)); }
 
+// Which incomplete length sets build_table accepts (the sets zlib's inflate
+// accepts, and the ones check_headers of inflate_gen.hip takes as candidates)
+enum TreeNeed {
+  TREE_ANY = 0,       // no test: the fixed tables (30 distance codes of 5 bits are incomplete by definition)
+  TREE_COMPLETE = 1,  // the code-length code
+  TREE_LITLEN = 2,    // complete, or one code of 1 bit
+  TREE_DIST = 3,      // complete, one code of 1 bit, or no code at all
+};
+
 // Build a canonical decode table from `n` code lengths in s->lens[off..off+n).
-// Returns 0, or ZT_E_BAD_TREE for an over-subscribed length set.
-__device__ __forceinline__ int build_table(const uint8_t *lens, int n, HuffTab *t, int lane, bool is_dist) {
+// Returns 0, or ZT_E_BAD_TREE for an over-subscribed length set or an
+// incomplete one that `need` does not allow.
+__device__ __forceinline__ int build_table(const uint8_t *lens, int n, HuffTab *t, int lane, bool is_dist,
+                                           int need) {
   if (lane < 16) {
     t->count[lane] = 0;
     t->running[lane] = 0;
@@ -83,6 +94,10 @@ __device__ __forceinline__ int build_table(const uint8_t *lens, int n, HuffTab *
       if (left < 0) st = ZT_E_BAD_TREE;
       if (t->count[l]) maxlen = l;
     }
+    if (left > 0 && need != TREE_ANY) {
+      const bool one = off == 1 && maxlen == 1;
+      if (!(one && need >= TREE_LITLEN) && !(off == 0 && need == TREE_DIST)) st = ZT_E_BAD_TREE;
+    }
     t->first[0] = 0;
     t->offs[0] = 0;
     for (int l = 1; l < 16; ++l) {
@@ -104,7 +119,7 @@ __device__ __forceinline__ int build_table(const uint8_t *lens, int n, HuffTab *
       if (l == L) peers = m;
     }
     uint32_t below = __popcll(peers & lanemask_lt(lane));
-    if (l) t->sorted[t->offs[l] + t->running[l] + below] = (uint16_t)s;
+    if (l) t->sorted[t->offs[l] + t->running[l] + below] = (int16_t)s;
     wave_sync();
     if (l && below == 0) t->running[l] += __popcll(peers);
     wave_sync();
@@ -119,14 +134,14 @@ __device__ __forceinline__ int build_table(const uint8_t *lens, int n, HuffTab *
       uint32_t c = r >> (32 - l);
       uint32_t k = c - t->first[l];
       if (k < t->count[l]) {
-        const uint32_t sym = t->sorted[t->offs[l] + k];
+        const uint32_t sym = (uint32_t)t->sorted[t->offs[l] + k];
         uint32_t ex = 0, base = 0;
         if (is_dist) {
           if (sym < 30) {
             ex = dist_extra(sym);
             base = dist_base(sym);
           }
-        } else if (sym > 256) {  // 286/287 decode as length 258, like the reference
+        } else if (sym > 256) {
           ex = len_extra(sym - 257);
           base = len_base(sym - 257);
         }
@@ -318,7 +333,8 @@ __device__ __forceinline__ int decode_sym(Reader &rd, const HuffTab *t, int &cle
     l = uni(l);
     if (l > (uint32_t)uni((uint32_t)t->maxlen)) return ZT_E_INVALID_SYMBOL;  // bits match no code of an incomplete set
     len = (int)l;
-    sym = (int)uni(t->sorted[t->base[l] + (int32_t)((uint32_t)r >> (32 - l))]);
+    sym = (int)uni((uint32_t)(int32_t)t->sorted[t->base[l] + (int32_t)((uint32_t)r >> (32 - l))]);
+    if (sym < 0) return ZT_E_INVALID_SYMBOL;  // the fixed code's 286 / 287 (read_tables)
   }
   clen = len;
   if (rd.past_end((uint32_t)len)) return ZT_E_INVALID_CODE_LENGTH;
@@ -340,10 +356,22 @@ __device__ int read_tables(Reader &rd, uint8_t *lens, HuffTab *lt, HuffTab *dt, 
     // fixed tables (RFC 1951 3.2.6)
     for (int s = lane; s < 288; s += 64) lens[s] = s <= 143 ? 8 : s <= 255 ? 9 : s <= 279 ? 7 : 8;
     wave_sync();
-    build_table(lens, 288, lt, lane, false);
+    build_table(lens, 288, lt, lane, false, TREE_ANY);
+    // 286 / 287 take part in the fixed code but never occur (RFC 1951 3.2.6).  At
+    // no cost to the decoders: their primary entries (8-bit codes 11000110 and
+    // 11000111, bit-reversed indices 0x63 and 0xE3 and every extension) become
+    // "long code", and the slots the long-code search then reads -- it takes the
+    // 9-bit prefixes 396..399 for codes of 9 bits, whose range starts at 400:
+    // sorted[offs[9] - 4 .. offs[9] - 1], after the primary table no longer needed
+    // -- hold -1, which every decoder already treats as "no such code".
+    static_assert(PRI == 8, "the fixed code's 286 / 287 (8 bits) must resolve through the 9-bit search");
+    for (int e = lane; e < (1 << PRI); e += 64)
+      if ((e & 0x7F) == 0x63) lt->pri[e] = 0;
+    if (lane < 4) lt->sorted[lt->offs[9] - 4 + lane] = -1;
+    wave_sync();
     for (int s = lane; s < 30; s += 64) lens[s] = 5;
     wave_sync();
-    build_table(lens, 30, dt, lane, true);
+    build_table(lens, 30, dt, lane, true, TREE_ANY);
     return ZT_OK;
   }
   if (btype != 2) {
@@ -369,7 +397,7 @@ __device__ int read_tables(Reader &rd, uint8_t *lens, HuffTab *lt, HuffTab *dt, 
   }
   wave_sync();
   if (!ok) return ZT_E_INPUT_BROKEN;
-  int bst = build_table(lens, 19, dt, lane, false);  // code-length code lives in `dt` for now
+  int bst = build_table(lens, 19, dt, lane, false, TREE_COMPLETE);  // code-length code lives in `dt` for now
   if (bst) return bst;
   const uint32_t total = hlit + hdist;
   for (int s = lane; s < 320; s += 64) lens[s] = 0;
@@ -411,8 +439,12 @@ __device__ int read_tables(Reader &rd, uint8_t *lens, HuffTab *lt, HuffTab *dt, 
   }
   wave_sync();
   if (status) return status;
-  bst = build_table(lens, (int)hlit, lt, lane, false);
-  if (!bst) bst = build_table(lens + hlit, (int)hdist, dt, lane, true);
+  // 286 / 287 never occur: a header that gives them a code is refused (the fixed
+  // code's are dealt with above)
+  if (hlit > 286 && (lens[286] | (hlit > 287 ? lens[287] : 0))) return ZT_E_BAD_TREE;
+  bst = build_table(lens, (int)hlit, lt, lane, false, TREE_LITLEN);
+  if (!bst && lens[256] == 0) bst = ZT_E_BAD_TREE;  // no end-of-block code: the block could never end
+  if (!bst) bst = build_table(lens + hlit, (int)hdist, dt, lane, true, TREE_DIST);
   return bst;
 }
 

@@ -899,9 +899,12 @@ void radix_sort64(std::vector<uint64_t> &v, uint64_t max_key) {
 // Host orchestration (see the file header).  Returns 0 with the output in
 // *d_out_io, 1 when the caller should decode with one wave (errors on the
 // chain -- the one-wave decoder reports them exactly -- or no convergence),
-// or a negative status.
-int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
-                        size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s) {
+// or a negative status.  A unit's token slot holds one token per 2 input bits
+// (+ the overlap past its stop); `dense`: one per bit, the format's maximum
+// (two 1-bit codes) -- kGenDense asks the caller for that second attempt.
+constexpr int kGenDense = 3;
+static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io, size_t out_cap,
+                       size_t *out_len, size_t *end_ip, hipStream_t s, bool dense) {
   if (n < index + (1u << 14)) return 1;
   const uint64_t bit0 = (uint64_t)index * 8, bitn = (uint64_t)n * 8;
   // ---- 1. candidates
@@ -1027,7 +1030,7 @@ int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t inde
     const uint64_t a = jobs[k].st.pos;
     const uint64_t b = k + 1 < units ? jobs[k + 1].st.pos : bitn;
     jobs[k].stop = k + 1 < units ? b : kNoStop;
-    uint64_t cap = (b - std::min(a, b)) / 2 + 8192;
+    uint64_t cap = (b - std::min(a, b)) / (dense ? 1 : 2) + 8192;
     cap = std::min<uint64_t>(cap, 1u << 30);
     jobs[k].tok_off = tok_total;
     jobs[k].tok_cap = (uint32_t)cap;
@@ -1102,6 +1105,11 @@ int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t inde
       if (!linked) {
         bad.push_back((uint32_t)k);
         clean = false;
+      }
+      if (clean && res[k].status == ZT_E_NOMEM && !dense) {
+        if (gen_debug())
+          fprintf(stderr, "[zt inflate gen] unit %zu on the chain: token slot full, again with one per bit\n", k);
+        return kGenDense;
       }
       if (clean && res[k].status != ZT_OK) GFALLBACK("unit %zu on the chain: status %d\n", k, res[k].status);
       if (res[k].end.kind == GK_FINAL && linked) {
@@ -1271,7 +1279,10 @@ int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t inde
   } else if (total > out_cap) {
     return set_error(ZT_E_ARG, "output capacity too small");
   }
-  if (total == 0) return ZT_OK;
+  if (total == 0) {
+    c->times.inflate_paths[1]++;
+    return ZT_OK;
+  }
   // ---- 4. expand, copy with markers, windows, final bytes
   void *d_chain, *d_desc, *d_o16, *d_win;
   const size_t chain_bytes = al256(chain.size() * sizeof(ChainUnit));
@@ -1354,6 +1365,13 @@ int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t inde
   c->times.inflate_paths[1]++;
   c->times.general_passes += (uint64_t)pass + 1;
   return ZT_OK;
+}
+
+int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
+                        size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s) {
+  int r = general_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s, false);
+  if (r == kGenDense) r = general_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s, true);
+  return r;
 }
 
 }  // namespace zt

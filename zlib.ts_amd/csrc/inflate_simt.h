@@ -38,7 +38,7 @@ __device__ __forceinline__ int long_code(const HuffTab *t, uint32_t v, uint32_t 
     const uint32_t k = c - uni(t->first[l]);
     if (k < uni(t->count[l])) {
       len = (uint32_t)l;
-      return (int)uni(t->sorted[uni(t->offs[l]) + k]);
+      return (int)uni((uint32_t)(int32_t)t->sorted[uni(t->offs[l]) + k]);
     }
   }
   return -1;
@@ -867,6 +867,9 @@ __device__ int tok_huffman_simt(Reader &rd, uint64_t b0, const HuffTab *lt, cons
     }
 #endif
     if (eob) {
+      // (an end-of-block code read from bits past the input's end -- zeros, or whatever
+      // follows the stream in its buffer -- does not end the block)
+      if (r_end > limit && __builtin_amdgcn_readlane(flags, e) == 1) return ZT_E_INPUT_BROKEN;
       end_bit = b0 + r_end;
       if (stopped) *stopped = __builtin_amdgcn_readlane(flags, e) == 3;
       return ZT_OK;
