@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "gunzip_chain.h"
 #include "zt_internal.h"
 
 namespace zt {
@@ -96,28 +97,6 @@ void put32le(uint8_t *p, uint32_t v) {
   p[3] = v >> 24;
 }
 
-// CRC-32 of a few host bytes (headers): table-free bitwise form, host logic only
-uint32_t crc32_small(const uint8_t *p, size_t n) {
-  uint32_t c = 0xFFFFFFFFu;
-  for (size_t i = 0; i < n; ++i) {
-    c ^= p[i];
-    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
-  }
-  return ~c;
-}
-
-// A byte of the input, or -1 past its end (the reference reads `undefined`).
-// u8(): the value a JS bitwise expression gives that byte (`undefined | x`
-// counts it as 0: ByteStream.readUint/readShort/readUintBE, src/ByteStream.ts:52-83).
-struct Reader {
-  const uint8_t *in;
-  size_t n, p;
-  int byte() { return p < n ? in[p++] : (++p, -1); }
-  uint32_t u8() { return p < n ? in[p++] : (++p, 0u); }
-};
-
-std::string num(int v) { return v < 0 ? std::string("undefined") : std::to_string(v); }
-
 }  // namespace
 
 // member header: src/GZip.ts:104-158
@@ -179,7 +158,6 @@ int zt_gunzip(const uint8_t *in, size_t n, uint8_t **out, size_t *out_len, zt_gz
   std::vector<zt_gzip_member> mem;
   std::vector<uint8_t> data;
   size_t ip = 0;
-  char msg[128];
   // the input goes to the device once; every member decodes from there
   DeviceCtx *c;
   ZT_TRY(get_ctx(&c));
@@ -189,89 +167,34 @@ int zt_gunzip(const uint8_t *in, size_t n, uint8_t **out, size_t *out_len, zt_gz
     ZT_TRY(scratch(c, 19, n + 64, &d_in));
     ZT_TRY(upload(c, d_in, in, n, c->stream));
   }
-  // src/GUnzip.ts:57-65: members until the input is consumed
+  // src/GUnzip.ts:57-65: members until the input is consumed (header and
+  // trailer checks: gunzip_chain.h, shared with zt_gunzip_batch)
   while (ip < n) {
     zt_gzip_member m;
-    memset(&m, 0, sizeof m);
-    Reader b{in, n, ip};
-    const int id1 = b.byte(), id2 = b.byte();
-    if (id1 != 0x1F || id2 != 0x8B) {
-      snprintf(msg, sizeof msg, "invalid file signature:%s,%s", num(id1).c_str(), num(id2).c_str());
-      return set_error(ZT_E_GZIP_SIGNATURE, msg);
-    }
-    const int cm = b.byte();
-    if (cm != 8) {
-      snprintf(msg, sizeof msg, "unknown compression method: %s", num(cm).c_str());
-      return set_error(ZT_E_GZIP_METHOD, msg);
-    }
-    const int flg = b.byte();
-    m.flg = (uint32_t)(flg < 0 ? 0 : flg);
-    uint32_t mt = 0;
-    for (int k = 0; k < 4; ++k) mt |= b.u8() << (8 * k);
-    m.mtime = mt;
-    m.xfl = b.u8();
-    m.os = b.u8();
-    if (m.flg & 0x04) {  // FEXTRA: skipped (src/GUnzip.ts:100-103,185-187)
-      const uint32_t lo = b.u8(), hi = b.u8();
-      m.xlen = lo | (hi << 8);
-      b.p += m.xlen;
-    }
-    if (m.flg & 0x08) {  // FNAME
-      m.name_off = b.p;
-      int ch;
-      while ((ch = b.byte()) > 0) {
-      }
-      m.name_len = b.p - 1 - m.name_off;
-    }
-    if (m.flg & 0x10) {  // FCOMMENT
-      m.comment_off = b.p;
-      int ch;
-      while ((ch = b.byte()) > 0) {
-      }
-      m.comment_len = b.p - 1 - m.comment_off;
-    }
-    if (m.flg & 0x02) {
-      // FHCRC: the reference takes the CRC of input[0 .. p), from the start of
-      // the whole input, not of the member (src/GUnzip.ts:127-131)
-      const uint32_t c16 = crc32_small(in, b.p < n ? b.p : n) & 0xFFFF;
-      const uint32_t lo = b.u8(), hi = b.u8();
-      m.has_crc16 = 1;
-      m.crc16 = c16;
-      if (c16 != (lo | (hi << 8))) return set_error(ZT_E_GZIP_HCRC, "invalid header crc16");
-    }
-    if (b.p > n) return set_error(ZT_E_INPUT_BROKEN, "input buffer is broken");
-    // body (src/GUnzip.ts:149-153): the engine's RawInflate from index b.p
+    GzError ge;
+    size_t body = 0;
+    if (gzip_parse_header(in, n, ip, &m, &body, &ge)) return set_error(ge.code, ge.msg);
+    // body (src/GUnzip.ts:149-153): the engine's RawInflate from index `body`
     uint8_t *o = nullptr;
     size_t olen = 0, eip = 0;
-    ZT_TRY(inflate_dev_member(c, (const uint8_t *)d_in, n, b.p, &o, &olen, &eip));
+    ZT_TRY(inflate_dev_member(c, (const uint8_t *)d_in, n, body, &o, &olen, &eip));
     uint32_t crc = 0;
     const int rc = zt_crc32_update(0, o, olen, &crc);
     if (rc) {
       zt_free(o);
       return rc;
     }
-    Reader t{in, n, eip};
-    uint32_t want = 0, isize = 0;
-    for (int k = 0; k < 4; ++k) want |= t.u8() << (8 * k);
-    if (crc != want) {
+    size_t next = 0;
+    if (gzip_check_trailer(in, n, eip, crc, olen, &m, &next, &ge)) {
       zt_free(o);
-      snprintf(msg, sizeof msg, "invalid CRC-32 checksum: 0x%x / 0x%x", crc, want);
-      return set_error(ZT_E_GZIP_CRC32, msg);
+      return set_error(ge.code, ge.msg);
     }
-    for (int k = 0; k < 4; ++k) isize |= t.u8() << (8 * k);
-    if ((uint32_t)olen != isize) {
-      zt_free(o);
-      snprintf(msg, sizeof msg, "invalid input size: %u / %u", (uint32_t)olen, isize);
-      return set_error(ZT_E_GZIP_ISIZE, msg);
-    }
-    m.crc32 = crc;
-    m.isize = isize;
     m.data_off = data.size();
     m.data_len = olen;
     data.insert(data.end(), o, o + olen);
     zt_free(o);
     mem.push_back(m);
-    ip = t.p;
+    ip = next;
   }
   uint8_t *h = host_out(data.size());
   if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");

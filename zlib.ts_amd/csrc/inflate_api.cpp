@@ -53,7 +53,7 @@ static bool bt_on() {
 
 static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<size_t> &in_off, const size_t *n,
                            const size_t *index, size_t count, uint8_t **out, size_t *out_len,
-                           std::vector<InfResult> &res, std::vector<size_t> &failed) {
+                           std::vector<InfResult> &res, std::vector<size_t> &failed, uint32_t *sums = nullptr) {
   hipStream_t s = c->stream;
   std::vector<size_t> ids;
   for (size_t i = 0; i < count; ++i) {
@@ -163,6 +163,22 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
   rp.marker = 0;
   rp.in = d_in;
   ZT_TRY(resolve_segments_dev(rp, s));
+  // (sums: CRC-32 and Adler-32 of every output where it lies in d_out, behind
+  // the resolve on the same stream; they come back with the statuses)
+  std::vector<uint32_t> hsums;
+  if (sums) {
+    std::vector<uint64_t> co(chain.size()), cl(chain.size());
+    for (size_t j = 0; j < chain.size(); ++j) {
+      co[j] = chain[j].out_off;  // 256-aligned
+      cl[j] = chain[j].out_len;
+    }
+    void *d_sums;
+    ZT_TRY(scratch(c, 18, 8 * chain.size(), &d_sums));
+    ZT_TRY(checksums_batch_dev(c, static_cast<const uint8_t *>(d_out), chain.size(), co.data(), cl.data(),
+                               static_cast<uint32_t *>(d_sums), s));
+    hsums.resize(2 * chain.size());
+    ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * chain.size(), hipMemcpyDeviceToHost, s));
+  }
   std::vector<int32_t> ust(chain.size()), sst(segs.size());
   ZT_HIP(hipMemcpyAsync(ust.data(), d_ust, chain.size() * 4, hipMemcpyDeviceToHost, s));
   ZT_HIP(hipMemcpyAsync(sst.data(), d_st, segs.size() * 4, hipMemcpyDeviceToHost, s));
@@ -193,6 +209,10 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
       r.end_ip = ((tr[k].end_bits + 7) >> 3) - in_off[i];
       r.status = ZT_OK;
       r.stop_idx = -1;
+      if (sums) {
+        sums[2 * i] = hsums[2 * j];
+        sums[2 * i + 1] = hsums[2 * j + 1];
+      }
     }
   }
   for (size_t j = 0; j < chain.size(); ++j)
@@ -207,10 +227,12 @@ int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<
                               const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
                               int *status);
 // (d_hist / hist_len: a preset dictionary's window, in front of every stream's
-// output: the one-wave decoder only, InfJob::hist)
+// output: the one-wave decoder only, InfJob::hist.  extras: see zt_internal.h)
 static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
                              const size_t *index, size_t count, int strict, uint8_t **out, size_t *out_len,
-                             size_t *end_ip, int *status, const uint8_t *d_hist = nullptr, uint32_t hist_len = 0) {
+                             size_t *end_ip, int *status, const uint8_t *d_hist = nullptr, uint32_t hist_len = 0,
+                             const BatchExtras *extras = nullptr) {
+  uint32_t *sums = extras ? extras->sums : nullptr;
   std::vector<size_t> cap(count);
   for (size_t i = 0; i < count; ++i) {
     // first guess (4x the stream's bytes from its start); exact sizes are
@@ -227,9 +249,24 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
   // non-strict batches of several streams: two-phase first, one wave per
   // stream for whatever it leaves (ZT_BATCH_ONEWAVE=1 forces the latter)
   static const bool onewave = getenv("ZT_BATCH_ONEWAVE") != nullptr;
-  if (!strict && count >= 8 && !onewave && !hist_len) {
-    ZT_TRY(batch_two_phase(c, (const uint8_t *)d_in, in_off, n, index, count, out, out_len, res, todo));
+  // (with extras, batches of any size: members of any length come through here)
+  if (!strict && (count >= 8 || extras) && !onewave && !hist_len) {
+    ZT_TRY(batch_two_phase(c, (const uint8_t *)d_in, in_off, n, index, count, out, out_len, res, todo, sums));
     std::sort(todo.begin(), todo.end());
+    if (extras && extras->speculative) {
+      std::vector<size_t> keep;
+      for (size_t i : todo) {
+        if (!extras->speculative[i]) {
+          keep.push_back(i);
+          continue;
+        }
+        res[i] = InfResult{};
+        res[i].status = ZT_E_INPUT_BROKEN;
+        out[i] = nullptr;
+        out_len[i] = 0;
+      }
+      todo.swap(keep);
+    }
   } else {
     todo.resize(count);
     for (size_t i = 0; i < count; ++i) todo[i] = i;
@@ -284,6 +321,22 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
         if (out_off[k] + r[k].out_len > span) span = out_off[k] + r[k].out_len;
       }
     }
+    // (sums: over the finished outputs' device copies, beside the download)
+    std::vector<uint32_t> hsums;
+    if (sums && !done.empty()) {
+      std::vector<uint64_t> co(done.size()), cl(done.size());
+      for (size_t j = 0; j < done.size(); ++j) {
+        co[j] = out_off[done[j]];  // 256-aligned
+        cl[j] = r[done[j]].out_len;
+      }
+      void *d_sums;
+      ZT_TRY(scratch(c, 18, 8 * done.size(), &d_sums));
+      ZT_TRY(checksums_batch_dev(c, static_cast<const uint8_t *>(d_out), done.size(), co.data(), cl.data(),
+                                 static_cast<uint32_t *>(d_sums), c->stream));
+      hsums.resize(2 * done.size());
+      ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * done.size(), hipMemcpyDeviceToHost, c->stream));
+      if (!span) ZT_HIP(hipStreamSynchronize(c->stream));
+    }
     if (span) {
       void *h;
       ZT_TRY(pinned(c, span, &h));
@@ -295,12 +348,17 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
         if (out_len[i]) memcpy(out[i], stage + out_off[k], out_len[i]);
       }, span);
     }
+    for (size_t j = 0; j < hsums.size() / 2; ++j) {
+      sums[2 * todo[done[j]]] = hsums[2 * j];
+      sums[2 * todo[done[j]] + 1] = hsums[2 * j + 1];
+    }
     todo.swap(again);
   }
   int first = ZT_OK;
   for (size_t i = 0; i < count; ++i) {
     status[i] = res[i].status;
     if (end_ip) end_ip[i] = res[i].end_ip;
+    if (extras && extras->detail) extras->detail[i] = res[i].detail;
     if (status[i] && first == ZT_OK) first = inflate_error(res[i].status, res[i].detail);
   }
   return first;
@@ -310,6 +368,13 @@ int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<
                               const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
                               int *status) {
   return inflate_dev_batch(c, d_in, in_off, n, index, count, 0, out, out_len, end_ip, status);
+}
+
+int inflate_batch_dev_streams_ex(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
+                                 const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
+                                 int *status, const uint8_t *d_hist, uint32_t hist_len, const BatchExtras *extras) {
+  return inflate_dev_batch(c, d_in, in_off, n, index, count, 0, out, out_len, end_ip, status, d_hist, hist_len,
+                           extras);
 }
 
 // Decode `count` host streams; outputs are malloc'd.

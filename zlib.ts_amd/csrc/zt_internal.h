@@ -252,6 +252,33 @@ int inflate_host_batch_hist(const uint8_t *const *in, const size_t *n, const siz
                             const uint8_t *d_hist, uint32_t hist_len, uint8_t **out, size_t *out_len, size_t *end_ip,
                             int *status);
 
+// device-resident streams (stream i at d_in + in_off[i], n[i] bytes, decoded
+// from index[i]) through the batch decoder -- two-phase, then one wave per
+// stream; with hist_len the one-wave decoder only, the history in front of
+// every stream (inflate_api.cpp).  Outputs are library memory (zt_free).
+// extras (optional): what the container batch calls need beside the bytes.
+struct BatchExtras {
+  uint32_t *sums = nullptr;  // [2 count]: CRC-32 and Adler-32 of every finished output, from its device copy
+  int *detail = nullptr;     // [count]: inflate_error's second argument for status[i]
+  // [count] or null: a stream with speculative[i] != 0 that the two-phase pass
+  // cannot finish is not decoded again by one wave; it gets ZT_E_INPUT_BROKEN,
+  // which is then no more than "failed" (not the reference's status)
+  const uint8_t *speculative = nullptr;
+};
+struct DeviceCtx;
+int inflate_batch_dev_streams_ex(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
+                                 const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
+                                 int *status, const uint8_t *d_hist, uint32_t hist_len, const BatchExtras *extras);
+
+// candidate gzip member starts of a packed batch (container.hip)
+struct MemberCand {
+  uint64_t off;   // offset in its item (> 0: the host adds every item's offset 0)
+  uint32_t item;
+  uint32_t pad;
+};
+int find_members_dev(const uint8_t *d_in, uint64_t total, const uint64_t *d_item_off, const uint64_t *d_item_len,
+                     uint32_t count, MemberCand *d_list, uint32_t cap, uint32_t *d_found, hipStream_t s);
+
 // ---- inflate jobs (one stream per wavefront) -----------------------------------
 struct InfJob {
   const uint8_t *in;  // whole input array (RawInflate's `input`)

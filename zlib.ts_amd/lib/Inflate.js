@@ -3,6 +3,7 @@
 // decompress() inflates on the GPU and, with `verify`, checks the Adler-32
 // (libzt zt_zlib_decompress).  `ip` is the reference's: past the stream.
 import native, { dflt, refError } from './native.js';
+import { batchError } from './GUnzip.js';
 
 export class Inflate {
     constructor(input, opts = {}) {
@@ -33,5 +34,29 @@ export class Inflate {
         this.ip = r.ip;
         if (this.verify) this.adler32 = r.adler32;
         return r.output;
+    }
+
+    // Many zlib streams in one call (zt_zlib_decompress_batch, with
+    // `dictionary` zt_zlib_decompress_batch_dict): an array with, per input,
+    // {output, ip, adler32} (adler32 only with `verify`) or, for a failed
+    // input, the Error the constructor or decompress() would throw (returned,
+    // not thrown).  This build's extra: the reference has no batch call.
+    static decompressBatch(inputs, opts = {}) {
+        const ins = Array.from(inputs, (x) => (x instanceof Uint8Array ? x : new Uint8Array(x)));
+        const verify = dflt(opts.verify, false);
+        const dict = opts.dictionary == null ? undefined
+            : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
+        let rs;
+        try {
+            rs = native.zlibDecompressBatch(ins, verify, dict);
+        } catch (e) {
+            throw refError(e);
+        }
+        return rs.map((r) => {
+            if (r.status !== undefined) return batchError(r);
+            const o = { output: r.output, ip: r.ip };
+            if (verify) o.adler32 = r.adler32;
+            return o;
+        });
     }
 }

@@ -14,6 +14,7 @@
 #include "../../include/zt.h"
 #include "../../include/zt_zipcrypto.h"
 #include "../../include/zt_dict.h"
+#include "../../include/zt_container_batch.h"
 
 namespace {
 
@@ -288,22 +289,10 @@ napi_value gzip_compress(napi_env env, napi_callback_info info) {
   return obj;
 }
 
-// gunzip(input) -> {output, members: [{flg, mtime, xfl, os, xlen, nameOff, nameLen, commentOff,
-//                   commentLen, crc16 (or -1), crc32, isize, dataOff, dataLen}]}
-napi_value gunzip(napi_env env, napi_callback_info info) {
-  napi_value a[1];
-  args(env, info, a, 1);
-  const uint8_t *p;
-  size_t n;
-  if (!get_u8(env, a[0], &p, &n)) return nullptr;
-  uint8_t *out = nullptr;
-  size_t olen = 0, cnt = 0;
-  zt_gzip_member *mem = nullptr;
-  int rc = zt_gunzip(p, n, &out, &olen, &mem, &cnt);
-  if (rc) return throw_zt(env, rc);
-  napi_value obj, arr;
-  napi_create_object(env, &obj);
-  napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
+// [{flg, mtime, xfl, os, xlen, nameOff, nameLen, commentOff, commentLen, crc16 (or -1), crc32, isize,
+//   dataOff, dataLen}] of cnt members
+napi_value members_array(napi_env env, const zt_gzip_member *mem, size_t cnt) {
+  napi_value arr;
   napi_create_array_with_length(env, cnt, &arr);
   for (size_t i = 0; i < cnt; ++i) {
     const zt_gzip_member &m = mem[i];
@@ -325,9 +314,135 @@ napi_value gunzip(napi_env env, napi_callback_info info) {
     set_num(env, e, "dataLen", (double)m.data_len);
     napi_set_element(env, arr, (uint32_t)i, e);
   }
+  return arr;
+}
+
+// gunzip(input) -> {output, members: [{flg, mtime, xfl, os, xlen, nameOff, nameLen, commentOff,
+//                   commentLen, crc16 (or -1), crc32, isize, dataOff, dataLen}]}
+napi_value gunzip(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  uint8_t *out = nullptr;
+  size_t olen = 0, cnt = 0;
+  zt_gzip_member *mem = nullptr;
+  int rc = zt_gunzip(p, n, &out, &olen, &mem, &cnt);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj;
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
+  napi_set_named_property(env, obj, "members", members_array(env, mem, cnt));
   zt_free(mem);
-  napi_set_named_property(env, obj, "members", arr);
   return obj;
+}
+
+// a failed item of a batch call: {status, message}
+napi_value batch_failure(napi_env env, int status, size_t i) {
+  napi_value e, m;
+  napi_create_object(env, &e);
+  set_num(env, e, "status", status);
+  napi_create_string_utf8(env, zt_container_batch_message(i), NAPI_AUTO_LENGTH, &m);
+  napi_set_named_property(env, e, "message", m);
+  return e;
+}
+
+bool get_u8_array(napi_env env, napi_value v, std::vector<const uint8_t *> &in, std::vector<size_t> &n) {
+  bool is_arr = false;
+  napi_is_array(env, v, &is_arr);
+  if (!is_arr) {
+    napi_throw_type_error(env, nullptr, "expected an array of Uint8Array");
+    return false;
+  }
+  uint32_t cnt = 0;
+  napi_get_array_length(env, v, &cnt);
+  in.resize(cnt);
+  n.resize(cnt);
+  for (uint32_t i = 0; i < cnt; ++i) {
+    napi_value e;
+    napi_get_element(env, v, i, &e);
+    if (!get_u8(env, e, &in[i], &n[i])) return false;
+  }
+  return true;
+}
+
+// gunzipBatch(inputs: Uint8Array[]) -> [{output, members} | {status, message}]  (zt_gunzip_batch)
+napi_value gunzip_batch(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  std::vector<const uint8_t *> in;
+  std::vector<size_t> n;
+  if (!get_u8_array(env, a[0], in, n)) return nullptr;
+  const size_t cnt = in.size();
+  std::vector<uint8_t *> out(cnt, nullptr);
+  std::vector<size_t> olen(cnt, 0), nm(cnt, 0);
+  std::vector<zt_gzip_member *> mem(cnt, nullptr);
+  std::vector<int> st(cnt, 0);
+  const int rc = zt_gunzip_batch(in.data(), n.data(), cnt, out.data(), olen.data(), mem.data(), nm.data(), st.data());
+  bool any = false;
+  for (int s : st) any = any || s != 0;
+  if (rc && !any) return throw_zt(env, rc);
+  napi_value arr;
+  napi_create_array_with_length(env, cnt, &arr);
+  for (size_t i = 0; i < cnt; ++i) {
+    napi_value e;
+    if (st[i]) {
+      e = batch_failure(env, st[i], i);
+    } else {
+      napi_create_object(env, &e);
+      napi_set_named_property(env, e, "output", new_u8(env, out[i], olen[i]));
+      napi_set_named_property(env, e, "members", members_array(env, mem[i], nm[i]));
+    }
+    zt_free(mem[i]);
+    napi_set_element(env, arr, (uint32_t)i, e);
+  }
+  return arr;
+}
+
+// zlibDecompressBatch(inputs: Uint8Array[], verify[, dictionary]) -> [{output, ip, adler32} | {status, message}]
+// (zt_zlib_decompress_batch / _dict; every stream from index 0)
+napi_value zlib_decompress_batch(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  const uint8_t *d;
+  size_t dn;
+  bool has_d;
+  if (!get_dict(env, a[2], &d, &dn, &has_d)) return nullptr;
+  std::vector<const uint8_t *> in;
+  std::vector<size_t> n;
+  if (!get_u8_array(env, a[0], in, n)) return nullptr;
+  bool verify = false;
+  napi_valuetype t;
+  napi_typeof(env, a[1], &t);
+  if (t == napi_boolean) napi_get_value_bool(env, a[1], &verify);
+  const size_t cnt = in.size();
+  std::vector<uint8_t *> out(cnt, nullptr);
+  std::vector<size_t> olen(cnt, 0), ip(cnt, 0);
+  std::vector<uint32_t> adler(cnt, 1);
+  std::vector<int> st(cnt, 0);
+  const int rc = has_d ? zt_zlib_decompress_batch_dict(in.data(), n.data(), nullptr, cnt, verify, d, dn, out.data(),
+                                                       olen.data(), ip.data(), adler.data(), st.data())
+                       : zt_zlib_decompress_batch(in.data(), n.data(), nullptr, cnt, verify, out.data(), olen.data(),
+                                                  ip.data(), adler.data(), st.data());
+  bool any = false;
+  for (int s : st) any = any || s != 0;
+  if (rc && !any) return throw_zt(env, rc);
+  napi_value arr;
+  napi_create_array_with_length(env, cnt, &arr);
+  for (size_t i = 0; i < cnt; ++i) {
+    napi_value e;
+    if (st[i]) {
+      e = batch_failure(env, st[i], i);
+    } else {
+      napi_create_object(env, &e);
+      napi_set_named_property(env, e, "output", new_u8(env, out[i], olen[i]));
+      set_num(env, e, "ip", (double)ip[i]);
+      set_num(env, e, "adler32", adler[i]);
+    }
+    napi_set_element(env, arr, (uint32_t)i, e);
+  }
+  return arr;
 }
 
 // zlibCompress(input, compressionType, lazy, level) -> {output, adler32}
@@ -538,6 +653,8 @@ napi_value init(napi_env env, napi_value exports) {
       {"gunzip", nullptr, gunzip, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"zlibCompress", nullptr, zlib_compress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"zlibDecompress", nullptr, zlib_decompress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"gunzipBatch", nullptr, gunzip_batch, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"zlibDecompressBatch", nullptr, zlib_decompress_batch, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"zipCompress", nullptr, zip_compress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"unzip", nullptr, unzip, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

@@ -81,6 +81,10 @@ class GzipMember(ctypes.Structure):
                 ("isize", ctypes.c_uint32), ("data_off", ctypes.c_size_t), ("data_len", ctypes.c_size_t)]
 
 
+class GunzipBatchStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("items", "candidates", "members", "decode_passes", "redecoded")]
+
+
 def _load():
     # torch (when present) ships its own libamdhip64.so.7; loading it first makes
     # libzt.so bind to that same runtime (same SONAME) instead of starting a
@@ -158,6 +162,14 @@ def _load():
         "zt_zlib_compress_batch_dict": ([P(vp), P(sz), sz, P(DeflateOpts), vp, sz, u8pp, P(sz), P(ctypes.c_int)],
                                         ctypes.c_int),
         "zt_zlib_decompress_dict": ([vp, sz, sz, ctypes.c_int, vp, sz, u8pp, P(sz), P(sz), P(u32)], ctypes.c_int),
+        # include/zt_container_batch.h
+        "zt_gunzip_batch": ([P(vp), P(sz), sz, u8pp, P(sz), P(P(GzipMember)), P(sz), P(ctypes.c_int)], ctypes.c_int),
+        "zt_zlib_decompress_batch": ([P(vp), P(sz), P(sz), sz, ctypes.c_int, u8pp, P(sz), P(sz), P(u32),
+                                      P(ctypes.c_int)], ctypes.c_int),
+        "zt_zlib_decompress_batch_dict": ([P(vp), P(sz), P(sz), sz, ctypes.c_int, vp, sz, u8pp, P(sz), P(sz), P(u32),
+                                           P(ctypes.c_int)], ctypes.c_int),
+        "zt_container_batch_message": ([sz], ctypes.c_char_p),
+        "zt_gunzip_batch_last_stats": ([P(GunzipBatchStats)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -193,6 +205,13 @@ ZIPCRYPTO_SYMBOLS = [
 DICT_SYMBOLS = [
     "zt_deflate_raw_dict", "zt_inflate_raw_dict", "zt_deflate_raw_batch_dict", "zt_inflate_raw_batch_dict",
     "zt_zlib_compress_dict", "zt_zlib_compress_batch_dict", "zt_zlib_decompress_dict",
+]
+
+
+# every symbol include/zt_container_batch.h declares (checked by tests/test_container_batch_host.py)
+CONTAINER_BATCH_SYMBOLS = [
+    "zt_gunzip_batch", "zt_zlib_decompress_batch", "zt_zlib_decompress_batch_dict", "zt_container_batch_message",
+    "zt_gunzip_batch_last_stats",
 ]
 
 
@@ -659,6 +678,101 @@ def zlib_decompress(data, index=0, verify=False, dictionary=None):
         _check(lib.zt_zlib_decompress(b, n, index, int(verify), ctypes.byref(out), ctypes.byref(olen),
                                       ctypes.byref(ip), ctypes.byref(adler)))
     return _take(out, olen), ip.value
+
+
+class BatchStatus(int):
+    """An item's status of a container batch call (an int: 0 = decoded) with
+    the item's message as `.message`."""
+
+    def __new__(cls, code, message=""):
+        self = super().__new__(cls, code)
+        self.message = message
+        return self
+
+
+def _batch_statuses(k, st):
+    return [BatchStatus(st[i], lib.zt_container_batch_message(i).decode(errors="replace") if st[i] else "")
+            for i in range(k)]
+
+
+def _member_dicts(raw, res, mem, cnt):
+    members = []
+    for i in range(cnt):
+        m = mem[i]
+        d = {k: getattr(m, k) for k, _ in GzipMember._fields_}
+        d["name"] = raw[m.name_off:m.name_off + m.name_len] if m.flg & 0x08 else None
+        d["comment"] = raw[m.comment_off:m.comment_off + m.comment_len] if m.flg & 0x10 else None
+        d["data"] = res[m.data_off:m.data_off + m.data_len]
+        members.append(d)
+    return members
+
+
+def gunzip_batch(items, return_code=False):
+    """zt_gunzip_batch: gunzip() of every item in one call.  Returns a list of
+    (status, output, members): status a BatchStatus (0, or the item's error
+    code with its message), members as gunzip() gives them; a failed item
+    has output None and no members.  return_code: also the call's return code
+    (the first failing item's), as (code, list)."""
+    bs, ptrs, lens = _batch_ptrs(items)
+    k = len(bs)
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    mems = (ctypes.POINTER(GzipMember) * k)()
+    cnts = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_gunzip_batch(ptrs, lens, k, outs, olens, mems, cnts, st)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    status = _batch_statuses(k, st)
+    res = []
+    for i in range(k):
+        if st[i] == 0:
+            data = ctypes.string_at(outs[i], olens[i])
+            res.append((status[i], data, _member_dicts(bs[i], data, mems[i], cnts[i])))
+        else:
+            res.append((status[i], None, []))
+        if outs[i]:
+            lib.zt_free(outs[i])
+        if mems[i]:
+            lib.zt_free(mems[i])
+    return (rc, res) if return_code else res
+
+
+def zlib_decompress_batch(items, verify=False, dictionary=None, index=None, return_code=False):
+    """zt_zlib_decompress_batch (dictionary: zt_zlib_decompress_batch_dict):
+    zlib_decompress() of every item in one call; index: one start per item.
+    Returns a list of (status, output, end ip, adler): status a BatchStatus,
+    adler the output's Adler-32 when verify is set, else 1; a failed item has
+    output None."""
+    bs, ptrs, lens = _batch_ptrs(items)
+    k = len(bs)
+    idx = (ctypes.c_size_t * k)(*index) if index is not None else None
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    ips = (ctypes.c_size_t * k)()
+    adl = (ctypes.c_uint32 * k)()
+    st = (ctypes.c_int * k)()
+    if dictionary is not None:
+        d, dn = _cbuf(dictionary)
+        rc = lib.zt_zlib_decompress_batch_dict(ptrs, lens, idx, k, int(verify), d, dn, outs, olens, ips, adl, st)
+    else:
+        rc = lib.zt_zlib_decompress_batch(ptrs, lens, idx, k, int(verify), outs, olens, ips, adl, st)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    status = _batch_statuses(k, st)
+    res = []
+    for i in range(k):
+        res.append((status[i], ctypes.string_at(outs[i], olens[i]) if st[i] == 0 else None, ips[i], adl[i]))
+        if outs[i]:
+            lib.zt_free(outs[i])
+    return (rc, res) if return_code else res
+
+
+def gunzip_batch_stats():
+    """Counters of this thread's last gunzip_batch call (zt_gunzip_batch_stats)."""
+    s = GunzipBatchStats()
+    _check(lib.zt_gunzip_batch_last_stats(ctypes.byref(s)))
+    return {f: int(getattr(s, f)) for f, _ in GunzipBatchStats._fields_}
 
 
 # ---- device-resident helpers (torch tensors as HBM buffers) -----------------------
