@@ -7,7 +7,8 @@
 //      consecutive 32 KiB blocks; a 1 MiB segment starts without history,
 //      later super-chunks index the 28 KiB before them first).  4 KiB
 //      sub-chunks stream through a 32 KiB LDS ring (28 608-byte window).
-//      Wave 0 links 8-byte-key hash chains (u16 heads, u16 relative links)
+//      Wave 0 links 8-byte-key hash chains (u16 relative links; u32 heads,
+//      u16 heads while a block measures through the queues below)
 //      and wave 1 a 4-byte-key table (the newest earlier position per
 //      bucket), each by lane-ordered LDS exchanges head[h] <-> p, 64
 //      positions per exchange, publishing their progress; all waves search
@@ -61,6 +62,8 @@ __device__ unsigned long long g_df_count[8];  // debug: pair steps (per wave), l
 #endif
 // blocks whose later sub-chunks measured through the queues / at once (zt_debug_match_modes)
 __device__ unsigned long long g_match_modes[2];
+// chain-head format changes of the match workgroups: u32 -> u16 / u16 -> u32 (zt_debug_head_formats)
+__device__ unsigned long long g_head_formats[2];
 
 #ifndef ZT_DF_BLOCK
 #define ZT_DF_BLOCK 32768
@@ -87,11 +90,12 @@ constexpr int DF_RING = 32768;  // power of two: ring index = rel & (DF_RING - 1
 // 17 + 19 * 3 + 316 * 14 bits); the coded block itself goes straight into the stream
 constexpr int DF_SLOT = 2048;
 static_assert(DF_SLOT >= 321 * 4 && DF_SLOT * 8 >= 17 + 19 * 3 + 316 * 14, "slot holds histograms and a header");
-// hash buckets of the 8-byte-key chains (u16 heads) and of the 4-byte-key
-// table (u32 heads, no chains): with the ring, the chain links, the
-// sub-chunk's 4-byte links and the waves' measurement queues they fill the
-// 160 KiB of LDS (u32 chain heads at the same count give the same streams;
-// their upper halves are the room the queues take)
+// hash buckets of the 8-byte-key chains and of the 4-byte-key table (u32
+// heads, no chains): with the ring, the chain links and the sub-chunk's
+// 4-byte links they fill the 160 KiB of LDS.  The chain heads are u32 while a
+// workgroup's blocks measure at once, and u16 -- two per word -- while they
+// measure through the waves' queues, which then take the room of the upper
+// halves (MatchShared); both formats give the same links and streams.
 #ifndef ZT_DF_HSIZE
 #define ZT_DF_HSIZE 12240  // (even: two u16 heads per word)
 #endif
@@ -163,6 +167,10 @@ struct DeflateParams {
   // rest of the block measures through the waves' queues (mq_pair_loop): the
   // same matches, found with fuller waves
   int mq_thr;
+  // chain-head format of match_kernel: 0: per block (u16 while the block's
+  // later sub-chunks measure through the queues, else u32), 16 / 32: that
+  // format throughout (ZT_DF_HEADS; 32 queues nothing: the host clears mq_thr)
+  int heads;
   // 1: parse_kernel and price_kernel walk the path window by window
   // (parse_block_regs) instead of lane-parallel (ZT_PARSE_SERIAL; the streams
   // do not depend on it)
@@ -542,12 +550,20 @@ constexpr int MQ_FLUSH = ZT_DF_MQ_FLUSH;
 struct MatchShared {
   uint32_t ring[DF_RING / 4 + 16];  // data ring + 64-byte mirror of its start
   uint16_t prev[DF_RING];           // relative chain links (0 = none)
-  uint32_t head[DF_HSIZE / 2];      // newest position (rel mod 2^16) per hash bucket, two buckets per word
+  // the chain heads in one of two formats (workgroup-uniform, match_body's
+  // fmt16; head_convert changes it in place): the queues exist only beside
+  // u16 heads
+  union {
+    uint32_t head32[DF_HSIZE];      // u32 format: newest position (rel) per hash bucket, kNoHead = none
+    struct {
+      uint32_t head[DF_HSIZE / 2];  // u16 format: newest position (rel mod 2^16) per hash bucket, two buckets per word
+      uint32_t mq[DF_THREADS / 64][MQ_RING];   // per wave: candidates to measure (distance | walk slot << 16), a ring
+      uint32_t mr[DF_THREADS / 64][MQ_SLOTS];  // per wave and walk slot: the best candidate's mq_key
+    };
+  };
   uint32_t head4[DF_H4SIZE];        // newest position (rel) per 4-byte-key bucket
   uint16_t link4[DF_SUB];           // position p of the sub-chunk: distance to the newest earlier
                                     // position of its 4-byte-key bucket (0 = none), at p % DF_SUB
-  uint32_t mq[DF_THREADS / 64][MQ_RING];       // per wave: candidates to measure (distance | walk slot << 16), a ring
-  uint32_t mr[DF_THREADS / 64][MQ_SLOTS];      // per wave and walk slot: the best candidate's mq_key
   uint32_t dummy[4];                // exchange / link targets of lanes past the end (branch-free chain_link)
   uint32_t linked;                  // positions below are linked (chain_link -> searching waves)
   uint32_t linked4;                 // positions below have their 4-byte links
@@ -558,6 +574,7 @@ struct MatchShared {
   int queued;                       // the block's later sub-chunks measure their candidates through the queues
 };
 static_assert(sizeof(MatchShared) <= 160 * 1024, "MatchShared fits the CU's LDS");
+static_assert(offsetof(MatchShared, head32) % 8 == 0, "head_convert moves u32 heads in pairs");
 
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
 // operations, not for its global loads (the next sub-chunk's prefetch stays
@@ -619,7 +636,12 @@ __device__ void load_sub(MatchShared *s, const uint8_t *g, uint32_t rel0, uint32
     ring_put32(s, (k0 >> 2) + t, reinterpret_cast<const uint32_t *>(g)[t]);
     return;
   }
-  for (uint32_t i = t; i < len; i += DF_THREADS) ring_put8(s, k0 + i, g[i]);
+  // (the rare path of a short or unaligned sub-chunk: its start index is opaque
+  // to the compiler, which would otherwise keep g + t in two registers across
+  // the whole sub-chunk loop of match_body)
+  uint32_t i0 = t;
+  __asm__ volatile("" : "+v"(i0));
+  for (uint32_t i = i0; i < len; i += DF_THREADS) ring_put8(s, k0 + i, g[i]);
 }
 
 // chain links for positions [lo, hi) (rel coords), by one wave, in position
@@ -630,8 +652,9 @@ __device__ void load_sub(MatchShared *s, const uint8_t *g, uint32_t rel0, uint32
 // ends at the step's last one.  Exchanges of later steps are issued without
 // waiting for earlier results (the wave's LDS operations stay in order); the
 // progress is published for the searching waves (match_kernel).  T = 0: the
-// 8-byte-key chains (head -> prev, s->linked); T = 1, by a second wave at the
-// same time: the 4-byte-key table (head4 -> link4, s->linked4).
+// 8-byte-key chains (head or head32 -> prev, s->linked; F16: the heads'
+// format); T = 1, by a second wave at the same time: the 4-byte-key table
+// (head4 -> link4, s->linked4).
 // Hashes of the keys at positions [lo, hi), by all threads of the workgroup,
 // parked in the slots their links will fill: prev[ridx(p)] (the ring slot of
 // p held a position 32 KiB back, out of every walk's reach) and
@@ -684,7 +707,7 @@ __device__ __forceinline__ void hash_keys(MatchShared *s, uint32_t lo, uint32_t 
 #define ZT_CL_U 8
 #endif
 constexpr int CL_U = ZT_CL_U;  // steps per group: hashes, then exchanges, then links
-template <int T>
+template <int T, bool F16 = false>
 __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
   const int lane = threadIdx.x & 63;
   const uint32_t nsteps = (hi - lo + 63) / 64;
@@ -704,7 +727,7 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
     // branch-free: lanes past hi exchange with / link into a dummy word, so
     // the compiler keeps every load and exchange of the group in flight
     uint32_t old[CL_U];
-    if (T == 0) {
+    if (T == 0 && F16) {
       // u16 heads: a masked-OR exchange of one half-word (ds_mskor_rtn_b32
       // applies a wave's conflicting lanes in lane order, as the exchange
       // does: tools/micro/lds_mskor_order.hip); the waits come after all CL_U
@@ -735,7 +758,7 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
 #pragma unroll
       for (int j = 0; j < CL_U; ++j) {
         const uint32_t p = lo + (sb + j) * 64 + lane;
-        uint32_t *hp = p < hi ? &s->head4[hq[j]] : &s->dummy[T];
+        uint32_t *hp = p < hi ? (T == 0 ? &s->head32[hq[j]] : &s->head4[hq[j]]) : &s->dummy[T];
         old[j] = atomicExch(hp, p);
       }
       hashes(sb + CL_U, hq);
@@ -777,6 +800,62 @@ __device__ __forceinline__ void head_sweep(MatchShared *s, uint32_t S) {
       if (age > (uint32_t)DF_MAXDIST && age < 65536u - 1024u) r = (r & ~(0xFFFFu << (16 * k))) | (stale << (16 * k));
     }
     if (r != w) s->head[i] = r;
+  }
+}
+
+// The workgroup's chain heads change their format in place, at rel position
+// S (a sub-chunk start, before that sub-chunk is linked; all threads, between
+// two barriers of match_body).  Every bucket gives the same link afterwards
+// for every later position as without the change:
+// u16 -> u32: a head in reach of S (or one of the <= DF_HEAD positions linked
+// ahead of S, as in head_sweep) becomes its exact rel position, every other
+// one kNoHead;
+// u32 -> u16: a head in reach or ahead keeps its low half, every other one
+// becomes S - 32768 -- the state a head_sweep at S leaves, so the sweep
+// schedule's bound holds from here as from a sweep.
+// The two arrays overlap: every thread reads its buckets, a barrier, then it
+// writes (the caller's next barrier comes before the link waves read them).
+__device__ __forceinline__ uint32_t head_to32(uint32_t v, uint32_t S) {
+  const uint32_t age = (S - v) & 0xFFFFu;
+  return age <= (uint32_t)DF_MAXDIST ? S - age : age >= 65536u - 1024u ? S + (65536u - age) : kNoHead;
+}
+__device__ __forceinline__ uint32_t head_to16(uint32_t r, uint32_t S) {
+  return (S - r <= (uint32_t)DF_MAXDIST || r - S <= 1024u) ? (r & 0xFFFFu) : ((S - 32768u) & 0xFFFFu);
+}
+template <bool TO16>
+__device__ __forceinline__ void head_convert(MatchShared *s, uint32_t S) {
+  constexpr uint32_t NW = (DF_HSIZE / 2 + DF_THREADS - 1) / DF_THREADS;  // bucket pairs per thread
+  uint32_t a[NW], b[NW];
+  // (opaque to the compiler: it would otherwise compute every thread's 12
+  // addresses ahead of the sub-chunk loop and spill them around the search)
+  uint32_t tid = threadIdx.x;
+  __asm__ volatile("" : "+v"(tid));
+#pragma unroll
+  for (uint32_t k = 0; k < NW; ++k) {
+    const uint32_t i = tid + k * DF_THREADS;
+    a[k] = b[k] = 0;
+    if (i < DF_HSIZE / 2) {
+      if (TO16) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(&s->head32[2 * i]);
+        a[k] = v.x;
+        b[k] = v.y;
+      } else {
+        const uint32_t w = s->head[i];
+        a[k] = w & 0xFFFFu;
+        b[k] = w >> 16;
+      }
+    }
+  }
+  lds_barrier();
+#pragma unroll
+  for (uint32_t k = 0; k < NW; ++k) {
+    const uint32_t i = tid + k * DF_THREADS;
+    if (i < DF_HSIZE / 2) {
+      if (TO16)
+        s->head[i] = head_to16(a[k], S) | head_to16(b[k], S) << 16;
+      else
+        *reinterpret_cast<uint2 *>(&s->head32[2 * i]) = make_uint2(head_to32(a[k], S), head_to32(b[k], S));
+    }
   }
 }
 
@@ -1369,7 +1448,13 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
   key.kmask2 = P.klen >= 8 ? 0xFFFFFFFFu : P.klen == 6 ? 0xFFFFu : P.klen == 5 ? 0xFFu : 0u;
   const uint32_t kext = (uint32_t)P.klen - 1;  // a key at p needs bytes up to p + kext
 
-  for (uint32_t i = t; i < DF_HSIZE / 2; i += DF_THREADS) s.head[i] = 0x80008000u;  // (rel 0 - 32768: out of reach)
+  // the chain heads' format (workgroup-uniform): u32 until a block queues
+  bool fmt16 = P.heads == 16;
+  if (fmt16) {
+    for (uint32_t i = t; i < DF_HSIZE / 2; i += DF_THREADS) s.head[i] = 0x80008000u;  // (rel 0 - 32768: out of reach)
+  } else {
+    for (uint32_t i = t; i < DF_HSIZE; i += DF_THREADS) s.head32[i] = kNoHead;
+  }
   for (uint32_t i = t; i < DF_H4SIZE; i += DF_THREADS) s.head4[i] = kNoHead;
   // the last kext positions of the first sub-chunk read link4 before any
   // link reached their slots: no candidate (not the LDS left by an earlier
@@ -1416,6 +1501,25 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
       }
       if (probe_sub) s.late = s.late2 = s.nmeas = 0;
     }
+    // the heads follow the block's way of measuring (the queues lie in the
+    // u32 heads' upper half): every thread derives the verdict thread 0
+    // stores in s.queued from the same count (complete since the barrier
+    // that closed the probe sub-chunk; no one writes it before the next
+    // probe), so the branch and its barrier are taken by all or by none
+    bool converted = false;
+    if (P.heads == 0 && P.mq_thr && p0 > rs && ((p0 - rs) % DF_BLOCK) == DF_SUB) {
+      const uint32_t nm = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.nmeas);
+      const bool want16 = (uint64_t)nm * 4096u >= (uint64_t)P.mq_thr * DF_SUB;
+      if (want16 != fmt16) {
+        if (want16)
+          head_convert<true>(&s, p0);
+        else
+          head_convert<false>(&s, p0);
+        if (t == 0) atomicAdd(&g_head_formats[want16 ? 0 : 1], 1ull);
+        fmt16 = want16;
+        converted = true;
+      }
+    }
     // the next sub-chunk is fetched while this one is searched
     const uint32_t n0 = p0 + DF_SUB;
     const bool fast = g_aligned && n0 + DF_SUB <= re;
@@ -1433,7 +1537,8 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
       pml = bend < dend ? bend : dend;
     }
     if (link) hash_keys(&s, inserted, ih, key);
-    if ((p0 / DF_SUB) % HEAD_SWEEP == 0 && link) head_sweep(&s, p0);
+    // (a change to u16 at p0 left the heads as a sweep at p0 does)
+    if (fmt16 && !converted && (p0 / DF_SUB) % HEAD_SWEEP == 0 && link) head_sweep(&s, p0);
     lds_barrier();
     DF_T(t1);
     // wave 0 links the 8-byte-key chains and wave 1 the 4-byte-key table,
@@ -1444,7 +1549,12 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
     // the linking waves are on every searcher's critical path: issue first
     if (t < 128 && link) __builtin_amdgcn_s_setprio(ZT_DF_LINK_PRIO);
 #endif
-    if (t < 64 && link) chain_link<0>(&s, inserted, ih, key);
+    if (t < 64 && link) {
+      if (fmt16)
+        chain_link<0, true>(&s, inserted, ih, key);
+      else
+        chain_link<0, false>(&s, inserted, ih, key);
+    }
     if (t >= 64 && t < 128 && link) chain_link<1>(&s, inserted, ih, key);
 #ifdef ZT_DF_LINK_PRIO
     if (t < 128 && link) __builtin_amdgcn_s_setprio(0);
@@ -3174,6 +3284,7 @@ struct DeflateLevel {
   int max_chain, nice, lazy, too_far, skip, klen, probe, good, opt;
   int adapt_depth = 0, adapt_thr = 0, adapt_depth2 = 0, adapt_thr2 = 0;  // per-block depth (DeflateParams)
   int mq_thr = 0;  // per-block queued measurement (DeflateParams; 0: never)
+  int heads = 0;   // chain-head format (DeflateParams; 0: per block)
   int parse_serial = 0;  // the serial window walk in parse / price (DeflateParams)
 };
 
@@ -3215,6 +3326,13 @@ static DeflateLevel level_params(int level) {
   // candidates per 4096 positions measure through the queues (0: none, 1:
   // every block whose probe measured anything); the streams do not depend on it
   if (const char *e = getenv("ZT_DF_MQ")) L.mq_thr = atoi(e) > 0 ? atoi(e) : 0;
+  // A/B and test hook: ZT_DF_HEADS=16: u16 chain heads throughout (the only
+  // format before the per-block choice); 32: u32 throughout, which leaves no
+  // room for the queues: no block queues; the streams do not depend on it
+  if (const char *e = getenv("ZT_DF_HEADS")) {
+    L.heads = atoi(e) == 16 ? 16 : atoi(e) == 32 ? 32 : 0;
+    if (L.heads == 32) L.mq_thr = 0;
+  }
   // A/B and test hook: ZT_PARSE_SERIAL=1: the serial window walk in
   // parse_kernel and price_kernel (the reference the lane-parallel walk is
   // tested against); the streams do not depend on it
@@ -3269,6 +3387,11 @@ static size_t deflate_geometry(const DeviceCtx *c, size_t n, DeflateGeom *g) {
   // tuning hook: ZT_DF_SUPER caps the blocks per workgroup (power of two <= 32)
   static const int cap_env = getenv("ZT_DF_SUPER") ? atoi(getenv("ZT_DF_SUPER")) : 0;
   const uint32_t cap = cap_env > 0 && cap_env <= 32 ? (uint32_t)cap_env : (uint32_t)((128u << 10) / DF_BLOCK);
+  // test hook: ZT_DF_SUPER_MIN = blocks per workgroup at least (within the
+  // cap): a small input in multi-block workgroups, as large inputs run (read
+  // per call; the streams do not depend on it)
+  const char *min_env = getenv("ZT_DF_SUPER_MIN");
+  if (min_env && atoi(min_env) > (int)kk) kk = (uint32_t)atoi(min_env);
   uint32_t k2 = 1;
   while (k2 < kk && k2 < cap) k2 <<= 1;
   g->k = k2;
@@ -3381,6 +3504,7 @@ int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, in
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
   P.mq_thr = L.mq_thr;
+  P.heads = L.heads;
   P.parse_serial = L.parse_serial;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
@@ -3506,6 +3630,7 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   P.adapt_depth2 = L.adapt_depth2;
   P.adapt_thr2 = L.adapt_thr2;
   P.mq_thr = L.mq_thr;
+  P.heads = L.heads;
   P.parse_serial = L.parse_serial;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
@@ -3577,6 +3702,15 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
 
 // blocks that measured through the queues, blocks that measured at once,
 // since the last call (of the current device)
+extern "C" int zt_debug_head_formats(uint64_t out[2]) {
+  unsigned long long v[2] = {}, z[2] = {};
+  ZT_HIP(hipDeviceSynchronize());
+  ZT_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_head_formats), sizeof v));
+  ZT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_head_formats), z, sizeof z));
+  out[0] = v[0];
+  out[1] = v[1];
+  return ZT_OK;
+}
 extern "C" int zt_debug_match_modes(uint64_t out[2]) {
   unsigned long long v[2] = {}, z[2] = {};
   ZT_HIP(hipDeviceSynchronize());

@@ -226,6 +226,10 @@ std::vector<int> batch_devices();                                     // zt_set_
 // match kernel that measured their candidates through the queues (out[0]) and
 // at once (out[1]) since the last call; reads and clears the device counter
 extern "C" int zt_debug_match_modes(uint64_t out[2]);
+// debug (deflate.hip): match workgroups that changed their chain heads from
+// u32 to u16 (out[0]) and from u16 to u32 (out[1]) since the last call; reads
+// and clears the device counter
+extern "C" int zt_debug_head_formats(uint64_t out[2]);
 // batch deflate (deflate.hip): streams packed at 32 KiB boundaries, one pipeline
 size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded);
 // a preset dictionary as the match kernel reads it (dict_host.h: dict_layout):

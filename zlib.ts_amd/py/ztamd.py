@@ -143,6 +143,7 @@ def _load():
         "zt_release_scratch": ([], ctypes.c_int),
         # debug (csrc/zt_internal.h)
         "zt_debug_match_modes": ([P(ctypes.c_uint64)], ctypes.c_int),
+        "zt_debug_head_formats": ([P(ctypes.c_uint64)], ctypes.c_int),
         # include/zt_zipcrypto.h
         "zt_zipcrypto_encrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
         "zt_zipcrypto_decrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
@@ -860,6 +861,14 @@ def debug_match_modes():
     their candidates, since the last call (reads and clears the device counter)."""
     v = (ctypes.c_uint64 * 2)()
     _check(lib.zt_debug_match_modes(v))
+    return int(v[0]), int(v[1])
+
+
+def debug_head_formats():
+    """(u32 -> u16, u16 -> u32): chain-head format changes of the deflate match
+    kernel's workgroups since the last call (reads and clears the device counter)."""
+    v = (ctypes.c_uint64 * 2)()
+    _check(lib.zt_debug_head_formats(v))
     return int(v[0]), int(v[1])
 
 
