@@ -1,4 +1,4 @@
-"""The deflate parse's two walks (csrc/deflate.hip): lane-parallel steps of
+"""The deflate parse's two walks (csrc/deflate_post.hip): lane-parallel steps of
 2048 positions (parse_block_lanes, the default) and the serial walk over
 64-position windows (parse_block_regs, ZT_PARSE_SERIAL=1).  Both emit the
 same tokens in the same order and count the same histograms, in parse_kernel

@@ -47,7 +47,7 @@ def test_per_generator_ratio(gate_rows):
 
 def test_adaptive_depth_engages_within_gate(oracle, gate_rows):
     """Level 6 chooses each block's search depth from its first 4 KiB
-    (deflate.hip DeflateParams::adapt_depth): on the source-text and
+    (zt_internal.h DeflateParams::adapt_depth): on the source-text and
     structured windows some blocks walk fewer hops than max_chain -- the
     streams differ from the fixed-depth ones (ZT_DF_ADAPT=0,0) -- and every
     window, adaptive or not, stays within the gate.  Streams decode through

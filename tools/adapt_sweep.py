@@ -1,4 +1,4 @@
-# Per-block search depth sweep (deflate.hip DeflateParams::adapt_depth /
+# Per-block search depth sweep (zt_internal.h DeflateParams::adapt_depth /
 # adapt_thr, ZT_DF_ADAPT="depth,thr"; "" = off): for each setting the
 # 16-window ratio gate of tests/ratio_corpus.py (per generator and the worst
 # window, this build's level-6 bytes over the reference's) and the match /

@@ -1,4 +1,4 @@
-// Host model of the lane-parallel parse walk of csrc/deflate.hip
+// Host model of the lane-parallel parse walk of csrc/deflate_post.hip
 // (parse_block_lanes): lanes as arrays, the same lane_walk and the same
 // entry-resolution loop, checked against the serial walk on random and
 // adversarial length arrays.  Prints the distribution of resolution rounds
@@ -14,7 +14,7 @@
 
 constexpr uint32_t PL_LANE = 32, PL_STEP = 64 * PL_LANE;
 
-// (as in deflate.hip; row[j]: the length at the lane's position j, 0 or 3..258)
+// (as in deflate_post.hip; row[j]: the length at the lane's position j, 0 or 3..258)
 static void lane_walk(const uint32_t *row, uint32_t mm, uint32_t e, uint32_t old, uint32_t &path, uint32_t &ex) {
   uint32_t p = 0, cur = e;
   bool merged = false;

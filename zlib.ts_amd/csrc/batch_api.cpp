@@ -4,7 +4,8 @@
 //
 // Per device, one pipeline for the whole share: the buffers are packed into
 // pinned staging at 32 KiB boundaries and uploaded with one copy; the batch
-// deflate pipeline (deflate.hip, one match workgroup per block so no history
+// deflate pipeline (deflate.hip's deflate_batch_dev_run: the match kernel, then
+// deflate_post.hip's stages; one match workgroup per block so no history
 // crosses buffers) runs on the main stream while the batched CRC-32 /
 // Adler-32 kernels read the same device bytes on the second stream; one copy
 // brings every stream back.  With zt_set_devices(mask) the buffers are split

@@ -9,12 +9,6 @@
 
 namespace zt {
 
-size_t deflate_bound_bytes(size_t n);
-size_t deflate_segment_bytes();
-size_t deflate_scratch_bytes(const DeviceCtx *c, size_t n);
-int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype, int level,
-                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s);
-
 static int resolve(const zt_deflate_opts *o, int *ctype, int *level) {
   int ct = o ? o->compression_type : 2;
   int lv = o ? o->level : -1;

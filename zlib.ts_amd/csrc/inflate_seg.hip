@@ -54,15 +54,9 @@ bool inf_debug() {
     if (inf_debug()) fprintf(stderr, "[zt inflate] " __VA_ARGS__); \
     return 1;                                           \
   } while (0)
-#ifndef ZT_DF_BLOCK
-#define ZT_DF_BLOCK 32768
-#endif
-#ifndef ZT_DF_GROUP
-#define ZT_DF_GROUP 1
-#endif
-// this engine's units are one DEFLATE block of ZT_DF_GROUP parse blocks
-// (deflate.hip): <= 1 token per byte
-constexpr uint32_t kUnitTokCap = ZT_DF_BLOCK * ZT_DF_GROUP + 64;
+// this engine's units are one DEFLATE block of DF_GROUP parse blocks
+// (zt_internal.h): <= 1 token per byte
+constexpr uint32_t kUnitTokCap = DF_BLOCK * DF_GROUP + 64;
 static_assert(kUnitTokCap < (1u << 30), "token counts stay below TokResult::ntok's flag bits");
 
 // sync point = byte after an aligned 00 00 FF FF; list entry = pos << 1 | restart

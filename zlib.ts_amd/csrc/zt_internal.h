@@ -198,6 +198,156 @@ __host__ __device__ __forceinline__ uint32_t dist_base(uint32_t ds) {  // 0..29
 }
 __host__ __device__ __forceinline__ uint32_t dist_extra(uint32_t ds) { return ds < 4 ? 0 : (ds >> 1) - 1; }
 
+// ---- deflate device pipeline ------------------------------------------------------
+// What deflate.hip (classify, match, the host driver) and deflate_post.hip
+// (price .. encode) share; inflate_seg.hip sizes its units from DF_BLOCK and
+// DF_GROUP.
+#ifdef ZT_DF_TIME
+#define DF_T(v) v = __builtin_readcyclecounter()  // debug: phase cycles (g_df_time, g_bk_time)
+#else
+#define DF_T(v) (void)0
+#endif
+#ifndef ZT_DF_BLOCK
+#define ZT_DF_BLOCK 32768
+#endif
+constexpr int DF_BLOCK = ZT_DF_BLOCK;
+// DEFLATE blocks (one Huffman code, one header, one sync point) may span
+// DF_GROUP consecutive 32 KiB parse blocks of a stream (compile option): the
+// match / price / DP / parse kernels keep their 32 KiB granularity,
+// block_kernel sums the group's histograms and encode_kernel writes the
+// group's tokens as one block.  Inflate units are one DEFLATE block
+// (inflate_seg.hip).  Measured at 4 (profiles/r03b_*): wordsalad ratio vs the
+// reference 1.0168 -> 1.0145 only, but inflate 10.9 -> 12.2 ms per GiB
+// (tokenize and expand get a quarter of the units): kept at 1.
+#ifndef ZT_DF_GROUP
+#define ZT_DF_GROUP 1
+#endif
+constexpr int DF_GROUP = ZT_DF_GROUP;
+static_assert(DF_GROUP >= 1 && DF_GROUP <= 8 && (32 % DF_GROUP) == 0, "group divides a segment");
+// per-block slot: the block's prices (price_kernel -> optparse_kernel), then
+// its histograms and token count (parse_kernel -> block_kernel), then its
+// dynamic header's complete words (block_kernel -> encode_kernel: at most
+// 17 + 19 * 3 + 316 * 14 bits); the coded block itself goes straight into the stream
+constexpr int DF_SLOT = 2048;
+static_assert(DF_SLOT >= 321 * 4 && DF_SLOT * 8 >= 17 + 19 * 3 + 316 * 14, "slot holds histograms and a header");
+// Independent segments of 1 MiB: restart points for segment-parallel inflate,
+// each announced by a restart marker (two empty stored blocks, deflate_post.hip)
+constexpr uint32_t kRestartBlocks = (1u << 20) / DF_BLOCK;  // 1 MiB
+constexpr uint32_t kRestartMarkerLen = 10;
+
+struct BlockPlan;
+
+struct DeflateParams {
+  const uint8_t *base;  // stream bytes are base[halo .. halo + n)
+  uint64_t halo;
+  uint64_t end;         // halo + n
+  uint32_t blocks_per_wg;
+  uint32_t big_wgs;     // match workgroups [0, big_wgs) take blocks_per_wg blocks, later ones tail_k
+  uint32_t tail_k;
+  uint32_t nblocks;
+  uint32_t restart;     // blocks per independent segment (multiple of blocks_per_wg)
+  uint32_t hist_max;    // history bytes a super-chunk loads (multiple of DF_SUB, <= DF_HIST)
+  int final_;
+  int max_chain;
+  int nice_len;
+  int lazy;
+  int too_far;
+  int good;             // a carried match this long cuts the chain walk to a quarter
+  int skip_len;         // a carried match at least this long is taken without a search
+  int klen;             // chain key length: 3, 4, 6 or 8 bytes (shorter matches come from near probes)
+  int probe;            // near distances 1..probe checked for matches shorter than klen
+  int ctype;            // 1: fixed codes only; 2: best of dynamic/fixed/stored
+  int opt;              // cost-based parse (optparse_kernel) between match and block kernels
+  // Per-block search depth (0: off): the block's first sub-chunk is searched
+  // with max_chain hops and counts the improvements its walks found at hop
+  // adapt_depth or later (and at hop adapt_depth2 or later); when the first
+  // are at most adapt_thr per 4096 positions, the rest of the block walks
+  // adapt_depth hops, else when the second are at most adapt_thr2,
+  // adapt_depth2 hops (match_kernel)
+  int adapt_depth, adapt_thr;
+  int adapt_depth2, adapt_thr2;
+  // Per-block candidate measurement (0: never queued): when the probe
+  // sub-chunk measured at least mq_thr candidates per 4096 positions, the
+  // rest of the block measures through the waves' queues (mq_pair_loop): the
+  // same matches, found with fuller waves
+  int mq_thr;
+  // chain-head format of match_kernel: 0: per block (u16 while the block's
+  // later sub-chunks measure through the queues, else u32), 16 / 32: that
+  // format throughout (ZT_DF_HEADS; 32 queues nothing: the host clears mq_thr)
+  int heads;
+  // 1: parse_kernel and price_kernel walk the path window by window
+  // (parse_block_regs) instead of lane-parallel (ZT_PARSE_SERIAL; the streams
+  // do not depend on it)
+  int parse_serial;
+  // batch of independent streams (zt_deflate_batch_dev): stream f occupies
+  // whole blocks from a 32 KiB-aligned offset; per block the [start, end) of
+  // its stream (relative to halo = 0), or null for one stream of n bytes
+  const uint64_t *span;
+  // per block: 1 = no match search, a stored block (classify_kernel: bytes
+  // that cannot beat stored); null when not classified
+  uint8_t *store;
+  uint32_t *nstore;     // blocks flagged (one counter, zeroed before classify_kernel)
+  uint32_t *res;        // n: per-position match, then (in place) per-block tokens
+  uint8_t *slots;       // nblocks x DF_SLOT (prices, histograms, dynamic headers)
+  uint32_t *slot_len;   // nblocks: each block's bytes (block_kernel's plan, exact)
+  uint8_t *out;         // the stream: encode_kernel writes block b at out + boff[b]
+  const uint64_t *boff; // exclusive scan of slot_len (+ restart markers), scan_sizes
+  uint32_t *fault;      // encode_kernel: a block's bits differ from its plan
+  BlockPlan *plans;     // nblocks
+};
+
+// per-block coding decisions (block_kernel -> encode_kernel)
+struct BlockPlan {
+  uint32_t lit_code[288];  // len << 16 | bit-reversed code
+  uint32_t dist_code[32];
+  uint32_t ntok;      // tokens of the group
+  uint32_t btype;     // 0 stored, 1 fixed, 2 dynamic
+  uint32_t hdr_bits;  // header bits (complete words already in the slot)
+  uint32_t hdr_tail;  // bits [hdr_bits & ~31, hdr_bits) of the header, not yet stored
+  uint32_t blen;      // input bytes of the group
+  uint32_t last;
+  uint32_t nsub;      // parse blocks in the group (<= DF_GROUP)
+  uint32_t pad;
+  uint32_t ntok_sub[8];  // tokens per parse block (in res at (leader + k) * DF_BLOCK)
+};
+
+// end of the stream block `blk` belongs to (relative to base + halo)
+__device__ __forceinline__ uint64_t stream_end(const DeflateParams &P, uint32_t blk) {
+  return P.span ? P.span[2 * (uint64_t)blk + 1] : P.end - P.halo;
+}
+
+// a DEFLATE block (group) starts at every DF_GROUP-th parse block of its
+// stream (batch: counted from the stream's first block)
+__device__ __forceinline__ bool group_leader(const DeflateParams &P, uint32_t blk) {
+  const uint64_t first = P.span ? P.span[2 * (uint64_t)blk] / DF_BLOCK : 0;
+  return ((blk - first) % DF_GROUP) == 0;
+}
+// parse blocks in the group led by `blk`
+__device__ __forceinline__ uint32_t group_size(const DeflateParams &P, uint32_t blk) {
+  const uint64_t lo = (uint64_t)blk * DF_BLOCK, n = stream_end(P, blk);
+  const uint64_t nb = (n - lo + DF_BLOCK - 1) / DF_BLOCK;
+  return nb < (uint64_t)DF_GROUP ? (uint32_t)nb : (uint32_t)DF_GROUP;
+}
+
+__device__ __forceinline__ uint64_t lanemask_lt(int lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
+
+// Per-position match word in res (match_kernel -> price / optparse / parse):
+// the byte at the position in bits 24-31 (so the later kernels never read
+// the input again), the match length (0 or 3..258) in bits 15-23 and its
+// distance (<= DF_MAXDIST < 2^15) in bits 0-14.  optparse_kernel rewrites the
+// length with its choice (0 = literal).
+__device__ __forceinline__ uint32_t res_pack(uint32_t byte, uint32_t len, uint32_t dist) {
+  return (byte << 24) | (len << 15) | dist;
+}
+__device__ __forceinline__ uint32_t res_len(uint32_t r) { return (r >> 15) & 511u; }
+__device__ __forceinline__ uint32_t res_dist(uint32_t r) { return r & 0x7FFFu; }
+__device__ __forceinline__ uint32_t res_byte(uint32_t r) { return r >> 24; }
+
+// The post-match stages (deflate_post.hip), launched on s in pipeline order:
+// price -> optparse (P.opt) -> parse -> block -> scan_sizes -> encode.  boff is
+// P.boff, writable: scan_sizes fills its nblocks + 1 entries.
+int deflate_post_run(const DeflateParams &P, uint64_t *boff, hipStream_t s);
+
 typedef __attribute__((address_space(1))) const uint8_t g_u8;
 typedef __attribute__((address_space(1))) const uint32_t g_u32;
 
@@ -230,6 +380,14 @@ extern "C" int zt_debug_match_modes(uint64_t out[2]);
 // u32 to u16 (out[0]) and from u16 to u32 (out[1]) since the last call; reads
 // and clears the device counter
 extern "C" int zt_debug_head_formats(uint64_t out[2]);
+// deflate (deflate.hip): one stream of n bytes at d_in (halo bytes of history
+// in front of it, final_: the last call of the stream) in one pipeline;
+// scratch of deflate_scratch_bytes(n), output of at most deflate_bound_bytes(n)
+size_t deflate_bound_bytes(size_t n);
+size_t deflate_segment_bytes();
+size_t deflate_scratch_bytes(const DeviceCtx *c, size_t n);
+int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype, int level,
+                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s);
 // batch deflate (deflate.hip): streams packed at 32 KiB boundaries, one pipeline
 size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded);
 // a preset dictionary as the match kernel reads it (dict_host.h: dict_layout):
