@@ -1,8 +1,9 @@
 """Host-only checks of the container batch calls: tools/gunzip_chain_check.cpp
 (the gzip header / trailer checks, the candidate bounds and the chain walk of
 zlib.ts_amd/csrc/gunzip_chain.h over hand-made candidate and decode tables)
-built with ASan + UBSan as a stand-alone program and run on the CPU, and the
-ABI of include/zt_container_batch.h."""
+built with ASan + UBSan as a stand-alone program and run on the CPU, the same
+for tools/inflate_chain_check.cpp (the segment and batch chains of
+zlib.ts_amd/csrc/inflate_chain.h), and the ABI of include/zt_container_batch.h."""
 import ctypes
 import os
 import re
@@ -24,6 +25,20 @@ def test_gunzip_chain_check_sanitized(tmp_path):
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert p.stdout.strip().endswith("gunzip_chain_check ok")
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="g++ missing")
+def test_inflate_chain_check_sanitized(tmp_path):
+    """tools/inflate_chain_check.cpp: the host chain logic of the two-phase
+    inflate (zlib.ts_amd/csrc/inflate_chain.h) over hand-made unit tables"""
+    exe = str(tmp_path / "inflate_chain_check")
+    b = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-o", exe, os.path.join(ROOT, "tools", "inflate_chain_check.cpp")],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-3000:]
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    assert p.stdout.strip().endswith("inflate_chain_check ok")
 
 
 def test_header_declares_what_the_binding_binds():

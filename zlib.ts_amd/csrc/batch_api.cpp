@@ -135,17 +135,17 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size
   }
   obsum = ooff[ng];
   void *d_in, *d_out, *d_scr, *d_sums = nullptr, *p;
-  ZT_TRY(scratch(c, 0, padded + 64, &d_in));
-  ZT_TRY(scratch(c, 1, obsum, &d_out));
+  ZT_TRY(scratch(c, kIn, padded + 64, &d_in));
+  ZT_TRY(scratch(c, kOut, obsum, &d_out));
   const size_t ss = deflate_batch_scratch_bytes(c, gmax);
-  ZT_TRY(scratch(c, 3, ss, &d_scr));
-  if (sums) ZT_TRY(scratch(c, 18, 8 * m, &d_sums));
+  ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
+  if (sums) ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
   uint8_t *stage_in[2], *stage_out;
-  ZT_TRY(pinned(c, gmax, &p, 0));
+  ZT_TRY(pinned(c, gmax, &p, kPinBatch));
   stage_in[0] = static_cast<uint8_t *>(p);
-  ZT_TRY(pinned(c, gmax, &p, 6));
+  ZT_TRY(pinned(c, gmax, &p, kPinGroupIn));
   stage_in[1] = static_cast<uint8_t *>(p);
-  ZT_TRY(pinned(c, obmax, &p, 7));
+  ZT_TRY(pinned(c, obmax, &p, kPinGroupOut));
   stage_out = static_cast<uint8_t *>(p);
   if (!c->up) ZT_HIP(hipStreamCreateWithFlags(&c->up, hipStreamNonBlocking));
   if (!c->dn) ZT_HIP(hipStreamCreateWithFlags(&c->dn, hipStreamNonBlocking));
@@ -309,7 +309,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
   if (hd.dict_len && ct != 0) {
     const DictLayout L = dict_layout(hd.dict_len);
     void *d_dict;
-    if (int rc = scratch(c, 29, L.hist, &d_dict)) return fail(rc);
+    if (int rc = scratch(c, kDict, L.hist, &d_dict)) return fail(rc);
     dict_img.resize(L.hist);
     dict_fill_history(L, hd.dict, dict_img.data());
     ZT_HIP(hipMemcpyAsync(d_dict, dict_img.data(), L.hist, hipMemcpyHostToDevice, c->stream));
@@ -344,8 +344,8 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     return rc ? fail(rc) : ZT_OK;
   }
   void *d_in, *h_stage;
-  if (int rc = scratch(c, 0, padded + 64, &d_in)) return fail(rc);
-  if (int rc = pinned(c, padded, &h_stage, 0)) return fail(rc);
+  if (int rc = scratch(c, kIn, padded + 64, &d_in)) return fail(rc);
+  if (int rc = pinned(c, padded, &h_stage, kPinBatch)) return fail(rc);
   uint8_t *stage = static_cast<uint8_t *>(h_stage);
   const double t_pack = stage_now();
   parallel_copy(m, [&](size_t k) {
@@ -363,7 +363,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     ~AuxWait() { (void)hipStreamSynchronize(s); }
   } aux_wait{c->aux};
   if (sums) {
-    if (int rc = scratch(c, 18, 8 * m, &d_sums)) return fail(rc);
+    if (int rc = scratch(c, kSums, 8 * m, &d_sums)) return fail(rc);
     ZT_HIP(hipEventRecord(c->aux_ev, c->stream));
     ZT_HIP(hipStreamWaitEvent(c->aux, c->aux_ev, 0));
     if (int rc = checksums_batch_dev(c, (const uint8_t *)d_in, m, off.data(), len.data(), (uint32_t *)d_sums, c->aux))
@@ -400,9 +400,9 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
   } else {
     const size_t ob = padded + padded / 8 + 1024 * (padded / kBlk + 1) + 4096;
     void *d_out, *d_scr;
-    if (int rc = scratch(c, 1, ob, &d_out)) return fail(rc);
+    if (int rc = scratch(c, kOut, ob, &d_out)) return fail(rc);
     const size_t ss = deflate_batch_scratch_bytes(c, padded);
-    if (int rc = scratch(c, 3, ss, &d_scr)) return fail(rc);
+    if (int rc = scratch(c, kDeflateOrDesc, ss, &d_scr)) return fail(rc);
     if (int rc = deflate_batch_dev_run(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv,
                                        (uint8_t *)d_out, oo.data(), d_scr, ss, c->stream, dh))
       return fail(rc);
@@ -425,7 +425,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     }
     const size_t fr_bytes = (tot + 255) & ~size_t(255), it_bytes = (m * sizeof(FrameItem) + 255) & ~size_t(255);
     void *d_fr;
-    if (int rc = scratch(c, 27, fr_bytes + it_bytes + plen + 256, &d_fr)) return fail(rc);
+    if (int rc = scratch(c, kFramed, fr_bytes + it_bytes + plen + 256, &d_fr)) return fail(rc);
     uint8_t *d_framed = static_cast<uint8_t *>(d_fr);
     FrameItem *d_items = reinterpret_cast<FrameItem *>(d_framed + fr_bytes);
     uint8_t *d_prefix = d_framed + fr_bytes + it_bytes;
@@ -615,12 +615,12 @@ int zt_crc32_batch(const uint8_t *const *in, const size_t *n, size_t count, uint
     tot += (n[i] + 255) & ~uint64_t(255);
   }
   void *d_in, *h, *d_sums;
-  ZT_TRY(scratch(c, 0, tot + 64, &d_in));
-  ZT_TRY(pinned(c, tot + 64, &h, 0));
+  ZT_TRY(scratch(c, kIn, tot + 64, &d_in));
+  ZT_TRY(pinned(c, tot + 64, &h, kPinBatch));
   uint8_t *stage = static_cast<uint8_t *>(h);
   parallel_copy(count, [&](size_t i) { copy_to_staging(stage + off[i], in[i], n[i]); }, tot);
   ZT_HIP(hipMemcpyAsync(d_in, stage, tot ? tot : 1, hipMemcpyHostToDevice, c->stream));
-  ZT_TRY(scratch(c, 18, 8 * count, &d_sums));
+  ZT_TRY(scratch(c, kSums, 8 * count, &d_sums));
   ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in, count, off.data(), len.data(), (uint32_t *)d_sums, c->stream));
   std::vector<uint32_t> sums(2 * count);
   ZT_HIP(hipMemcpyAsync(sums.data(), d_sums, 8 * count, hipMemcpyDeviceToHost, c->stream));

@@ -731,15 +731,18 @@ int checksums_batch_dev(DeviceCtx *c, const uint8_t *frame, size_t count, const 
   }
   first[count] = (uint32_t)jobs.size();
   const size_t nj = jobs.size();
-  const size_t jb = (nj * sizeof(CkJob) + 255) & ~size_t(255), fb = ((count + 1) * 4 + 255) & ~size_t(255);
-  const size_t lb = (count * 8 + 255) & ~size_t(255), sb = ((nj ? nj : 1) * sizeof(SegResult) + 255) & ~size_t(255);
-  void *buf;
-  ZT_TRY(scratch(c, 9, jb + fb + lb + sb, &buf));
-  uint8_t *b = static_cast<uint8_t *>(buf);
-  CkJob *d_jobs = reinterpret_cast<CkJob *>(b);
-  uint32_t *d_first = reinterpret_cast<uint32_t *>(b + jb);
-  uint64_t *d_len = reinterpret_cast<uint64_t *>(b + jb + fb);
-  SegResult *d_seg = reinterpret_cast<SegResult *>(b + jb + fb + lb);
+  CkJob *d_jobs = nullptr;
+  uint32_t *d_first = nullptr;
+  uint64_t *d_len = nullptr;
+  SegResult *d_seg = nullptr;
+  ZT_TRY(scratch_carved(c, kCkBatch, [&](void *base) {
+    Carve cv(base);
+    d_jobs = cv.take<CkJob>(nj);
+    d_first = cv.take<uint32_t>(count + 1);
+    d_len = cv.take<uint64_t>(count);
+    d_seg = cv.take<SegResult>(nj ? nj : 1);
+    return cv.bytes();
+  }));
   // small tables: blocking copies (the kernels below stay asynchronous)
   if (nj) ZT_HIP(hipMemcpy(d_jobs, jobs.data(), nj * sizeof(CkJob), hipMemcpyHostToDevice));
   ZT_HIP(hipMemcpy(d_first, first.data(), (count + 1) * 4, hipMemcpyHostToDevice));
@@ -762,7 +765,7 @@ int checksums_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, bool do_crc, bool
   const size_t lo = addr & 15, hi = lo + n;
   const size_t nseg = n ? (hi + CK_SEG - 1) / CK_SEG : 1;
   void *segbuf;
-  ZT_TRY(scratch(c, 8, nseg * sizeof(SegResult), &segbuf));
+  ZT_TRY(scratch(c, kCkSeg, nseg * sizeof(SegResult), &segbuf));
   SegResult *segs = static_cast<SegResult *>(segbuf);
   size_t g = nseg < (size_t)c->num_cu * 8 ? nseg : (size_t)c->num_cu * 8;
   if (g > (size_t)kCkMaxWg) g = kCkMaxWg;  // (one partial slot per workgroup)

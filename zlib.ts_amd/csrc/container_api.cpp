@@ -44,11 +44,11 @@ int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *o
   ZT_TRY(resolve_deflate(opts, &ct, &lv));
   const size_t ob = (ct == 0 ? n + 5 * ((n + 65534) / 65535) + 16 : deflate_bound_bytes(n) + (ct == 1 ? n / 8 + 64 : 0));
   void *d_in, *d_out, *d_scr, *d_res;
-  ZT_TRY(scratch(c, 0, n + 64, &d_in));
-  ZT_TRY(scratch(c, 1, ob, &d_out));
+  ZT_TRY(scratch(c, kIn, n + 64, &d_in));
+  ZT_TRY(scratch(c, kOut, ob, &d_out));
   const size_t ss = deflate_scratch_bytes(c, n);
-  ZT_TRY(scratch(c, 3, ss, &d_scr));
-  ZT_TRY(scratch(c, 2, 16, &d_res));
+  ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
+  ZT_TRY(scratch(c, kSmall, 16, &d_res));
   ZT_TRY(upload(c, d_in, in, n, c->stream));
   // the checksums run on the second stream beside the deflate pipeline (both
   // only read the input); every return below waits for that stream first
@@ -159,7 +159,7 @@ int zt_gunzip(const uint8_t *in, size_t n, uint8_t **out, size_t *out_len, zt_gz
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   void *d_in = nullptr;
   if (n) {
-    ZT_TRY(scratch(c, 19, n + 64, &d_in));
+    ZT_TRY(scratch(c, kContainerIn, n + 64, &d_in));
     ZT_TRY(upload(c, d_in, in, n, c->stream));
   }
   // src/GUnzip.ts:57-65: members until the input is consumed (header and

@@ -45,8 +45,6 @@ thread_local zt_gunzip_batch_stats t_stats = {0, 0, 0, 0, 0};
 // (a decode call that fails as a whole -- device memory, HIP -- leaves kNotRun)
 constexpr int kNotRun = -0x7FFF;
 
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
 // library outputs not handed to the caller are released on every return
 struct Outputs {
   std::vector<uint8_t *> p;
@@ -67,7 +65,7 @@ std::string inflate_message(int status, int detail) {
   return zt_last_error_message();
 }
 
-// items `ids` packed at 256-byte offsets into scratch slot 0, uploaded in
+// items `ids` packed at 256-byte offsets into scratch slot kIn, uploaded in
 // chunks of about 32 MiB as they are packed
 int pack_upload(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids,
                 std::vector<size_t> &in_off, size_t *total, void **d_in) {
@@ -76,10 +74,10 @@ int pack_upload(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const s
   size_t tot = 0;
   for (size_t k = 0; k < m; ++k) {
     in_off[k] = tot;
-    tot += align256(n[ids[k]] ? n[ids[k]] : 1);
+    tot += align_up(n[ids[k]] ? n[ids[k]] : 1, 256);
   }
   *total = tot;
-  ZT_TRY(scratch(c, 0, tot + 64, d_in));
+  ZT_TRY(scratch(c, kIn, tot + 64, d_in));
   void *h;
   ZT_TRY(pinned(c, tot, &h));
   uint8_t *stage = static_cast<uint8_t *>(h);
@@ -117,13 +115,17 @@ int gunzip_share_locked(DeviceCtx *c, const GunzipArgs &A, const std::vector<siz
   // candidates: the list's capacity is proportional to the packed input (one
   // per item and per 256 bytes; gz_slack keeps the decode scratch in proportion)
   const uint32_t cap = (uint32_t)std::min<size_t>(m + total / 256, 0x7FFFFFFFu);
-  const size_t tab_bytes = align256(m * 8), list_bytes = align256((size_t)cap * sizeof(MemberCand));
-  void *d_scan;
-  ZT_TRY(scratch(c, 19, 2 * tab_bytes + list_bytes + 256, &d_scan));
-  uint64_t *d_ioff = static_cast<uint64_t *>(d_scan);
-  uint64_t *d_ilen = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_scan) + tab_bytes);
-  MemberCand *d_list = reinterpret_cast<MemberCand *>(static_cast<uint8_t *>(d_scan) + 2 * tab_bytes);
-  uint32_t *d_found = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_scan) + 2 * tab_bytes + list_bytes);
+  uint64_t *d_ioff = nullptr, *d_ilen = nullptr;
+  MemberCand *d_list = nullptr;
+  uint32_t *d_found = nullptr;
+  ZT_TRY(scratch_carved(c, kContainerIn, [&](void *base) {
+    Carve cv(base);
+    d_ioff = cv.take<uint64_t>(m);
+    d_ilen = cv.take<uint64_t>(m);
+    d_list = cv.take<MemberCand>(cap);
+    d_found = cv.take<uint32_t>(1);
+    return cv.bytes();
+  }));
   std::vector<uint64_t> ioff(m), ilen(m);
   for (size_t k = 0; k < m; ++k) {
     ioff[k] = in_off[k];
@@ -392,7 +394,7 @@ int zlib_share_locked(DeviceCtx *c, const ZlibArgs &A, const std::vector<size_t>
   if (!part[1].empty()) {  // this device's copy of the dictionary's window
     wlen = dict_window_len(A.dict_len);
     void *p;
-    ZT_TRY(scratch(c, 29, wlen, &p));
+    ZT_TRY(scratch(c, kDict, wlen, &p));
     ZT_HIP(hipMemcpyAsync(p, A.dict + dict_window_off(A.dict_len), wlen, hipMemcpyHostToDevice, c->stream));
     ZT_HIP(hipStreamSynchronize(c->stream));
     d_hist = static_cast<const uint8_t *>(p);

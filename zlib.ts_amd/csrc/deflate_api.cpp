@@ -154,10 +154,10 @@ static int deflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, int 
     pmax = std::max(pmax, sizes[i]);
   }
   void *d_in, *d_out, *d_scr;
-  ZT_TRY(scratch(c, 0, n + 64, &d_in));
-  ZT_TRY(scratch(c, 1, out_off[np], &d_out));
+  ZT_TRY(scratch(c, kIn, n + 64, &d_in));
+  ZT_TRY(scratch(c, kOut, out_off[np], &d_out));
   const size_t ss = deflate_scratch_bytes(c, pmax);
-  ZT_TRY(scratch(c, 3, ss, &d_scr));
+  ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
   PipeOut po;
   po.base = host_out(out_off[np], true);
   po.cap = out_off[np];
@@ -194,10 +194,10 @@ int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uin
   if (ct != 0 && n >= kPipeMin) return deflate_raw_pipelined(c, in, n, ct, lv, out, out_len);
   const size_t ob = out_bound(ct, n);
   void *d_in, *d_out, *d_scr;
-  ZT_TRY(scratch(c, 0, n + 64, &d_in));
-  ZT_TRY(scratch(c, 1, ob, &d_out));
+  ZT_TRY(scratch(c, kIn, n + 64, &d_in));
+  ZT_TRY(scratch(c, kOut, ob, &d_out));
   const size_t ss = deflate_scratch_bytes(c, n);
-  ZT_TRY(scratch(c, 3, ss, &d_scr));
+  ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
   ZT_TRY(upload(c, d_in, in, n, c->stream));
   size_t len = 0;
   ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in, n, 0, 1, ct, lv, (uint8_t *)d_out, &len, d_scr, ss, c->stream));
@@ -247,8 +247,7 @@ int zt_inflate_dev(zt_inflate_plan *plan, const void *d_in, size_t n, void *d_ou
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   uint8_t *o = (uint8_t *)d_out;
   size_t ol = 0, eip = 0;
-  int seg = inflate_segments_dev(c, (const uint8_t *)d_in, n, 0, &o, out_cap, &ol, &eip, s);
-  if (seg >= 1) seg = inflate_general_dev(c, (const uint8_t *)d_in, n, 0, &o, out_cap, &ol, &eip, s);
+  const int seg = inflate_parallel_dev(c, (const uint8_t *)d_in, n, 0, &o, out_cap, &ol, &eip, s);
   if (seg < 0) return seg;
   if (seg == 0) {
     *out_len = ol;

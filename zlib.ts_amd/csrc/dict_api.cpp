@@ -34,7 +34,7 @@ int inflate_share(int dev, const uint8_t *const *in, const size_t *n, const size
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   const uint32_t wlen = dict_window_len(dict_len);
   void *d_hist;
-  if (int rc = scratch(c, 29, wlen, &d_hist)) return fail(rc);
+  if (int rc = scratch(c, kDict, wlen, &d_hist)) return fail(rc);
   if (hipMemcpyAsync(d_hist, dict + dict_window_off(dict_len), wlen, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return fail(set_error(ZT_E_HIP, "dictionary upload failed"));

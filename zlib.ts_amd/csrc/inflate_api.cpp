@@ -1,7 +1,6 @@
 // inflate_api.cpp -- host side of the inflate entry points (include/zt.h).
 #include <algorithm>
 #include <cstdio>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -32,7 +31,31 @@ int inflate_error(int status, int detail) {
   }
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// The large-stream cascade (zt_internal.h).
+int inflate_parallel_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
+                         size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary,
+                         bool allow_general) {
+  const bool library_out = *d_out_io == nullptr;
+  const int seg = inflate_segments_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s, boundary);
+  // (no sync points, or a stream they cannot finish: speculative parallel decode at arbitrary bit offsets)
+  if (seg != 1 || !allow_general) return seg;
+  if (library_out) *d_out_io = nullptr;
+  return inflate_general_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s);
+}
+
+// A decoded stream's `ol` device bytes into a host buffer the caller frees with zt_free.
+static int download_result(DeviceCtx *c, const uint8_t *d_out, size_t ol, bool pool, uint8_t **out, size_t *out_len) {
+  uint8_t *h = host_out(ol, pool);
+  if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
+  const int rc = download(c, h, d_out, ol, c->stream);
+  if (rc) {
+    zt_free(h);
+    return rc;
+  }
+  *out = h;
+  *out_len = ol;
+  return ZT_OK;
+}
 
 // Two-phase batch decode (inflate_tok.hip applied per stream): one tokenize
 // wave per stream (no history ring in LDS, so many streams per CU), then
@@ -41,15 +64,7 @@ static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // appended to `failed` for the one-wave decoder, which also yields the
 // reference's exact error. Outputs of the others are malloc'd and filled.
 // ZT_BATCH_TIMING=1: host wall time of the batch stages on stderr (measurement only)
-static double bt_now() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-static bool bt_on() {
-  static const bool on = getenv("ZT_BATCH_TIMING") != nullptr;
-  return on;
-}
-#define BT(label) \
-  if (bt_on()) fprintf(stderr, "[batch] %-28s %8.2f ms\n", label, bt_now())
+#define BT(label) ZT_STAMP("ZT_BATCH_TIMING", "batch", label)
 
 static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<size_t> &in_off, const size_t *n,
                            const size_t *index, size_t count, uint8_t **out, size_t *out_len,
@@ -88,24 +103,27 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
     j.stop_first = 0;
     tok_total += align_up(cap, 64);
   }
-  void *d_tok, *d_meta;
-  ZT_TRY(scratch(c, 4, (tok_total + 256) * 4, &d_tok));  // + slack: chunked token reads
-  const size_t jobs_bytes = align_up(units * sizeof(TokJob), 256);
-  ZT_TRY(scratch(c, 6, jobs_bytes + align_up(units * sizeof(TokResult), 256), &d_meta));
-  TokJob *d_jobs = static_cast<TokJob *>(d_meta);
-  TokResult *d_tres = reinterpret_cast<TokResult *>(static_cast<uint8_t *>(d_meta) + jobs_bytes);
+  void *d_tok;
+  ZT_TRY(scratch(c, kTokens, (tok_total + 256) * 4, &d_tok));  // + slack: chunked token reads
+  TokJob *d_jobs = nullptr;
+  TokResult *d_tres = nullptr;
+  ZT_TRY(scratch_carved(c, kTokMeta, [&](void *base) {
+    Carve cv(base);
+    d_jobs = cv.take<TokJob>(units);
+    d_tres = cv.take<TokResult>(units);
+    return cv.bytes();
+  }));
   ZT_HIP(hipMemcpyAsync(d_jobs, jobs.data(), units * sizeof(TokJob), hipMemcpyHostToDevice, s));
   TokParams tp{};
   tp.in = d_in;
   tp.n = 0;
-  tp.stops = reinterpret_cast<const uint64_t *>(d_meta);  // never read: nstops = 0
+  tp.stops = reinterpret_cast<const uint64_t *>(d_jobs);  // never read: nstops = 0
   tp.nstops = 0;
   tp.jobs = d_jobs;
   tp.res = d_tres;
   tp.tokens = static_cast<uint32_t *>(d_tok);
   tp.count = (uint32_t)units;
-  static const char *simt_env = getenv("ZT_TOK_SIMT");  // (A/B: 0 = one-lane body decode)
-  tp.simt = simt_env ? atoi(simt_env) != 0 : 1;
+  tp.simt = tok_simt_env();
   tp.dbg = nullptr;
   tp.dump_unit = 0xFFFFFFFFu;
   tp.dump_once = 0;
@@ -116,53 +134,20 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
   ZT_TRY(readback(c, tr.data(), d_tres, units * sizeof(TokResult), s));
   BT("tokenize done");
   // one chain unit and one segment per stream that decoded to BFINAL
-  std::vector<ChainUnit> chain;
-  std::vector<SegJob> segs;
-  std::vector<size_t> who;
-  uint64_t out_total = 0, desc_total = 0;
-  for (size_t k = 0; k < units; ++k) {
-    const TokResult &r = tr[k];
-    if (r.status != ZT_OK || r.stop_idx >= 0 || r.out_len > 0xFFFFFFFFull) {
-      failed.push_back(ids[k]);
-      continue;
-    }
-    desc_total = align_up(desc_total, 512);
-    // (a stream of stored runs only: expand_kernel writes it straight from
-    // the input, copy_kernel skips its segment -- inflate_seg.hip)
-    const bool direct = (r.ntok >> 30) == 3u;
-    segs.push_back(SegJob{(uint32_t)chain.size(), direct ? 0x80000001u : 1u});
-    chain.push_back(ChainUnit{jobs[k].tok_off, out_total, out_total, desc_total, r.ntok, (uint32_t)r.out_len});
-    who.push_back(k);
-    out_total += align_up(r.out_len ? r.out_len : 1, 256);
-    desc_total += r.out_len;
-  }
+  std::vector<uint64_t> tok_off(units);
+  for (size_t k = 0; k < units; ++k) tok_off[k] = jobs[k].tok_off;
+  const BatchChain bc = batch_chain_host(tr.data(), tok_off.data(), units);
+  const std::vector<ChainUnit> &chain = bc.chain;
+  const std::vector<SegJob> &segs = bc.segs;
+  const std::vector<size_t> &who = bc.who;
+  const uint64_t out_total = bc.out_total;
+  for (const size_t k : bc.failed) failed.push_back(ids[k]);
   if (chain.empty()) return ZT_OK;
-  void *d_out, *d_chain, *d_desc;
-  ZT_TRY(scratch(c, 1, out_total, &d_out));
-  const size_t chain_bytes = align_up(chain.size() * sizeof(ChainUnit), 256);
-  const size_t seg_bytes = align_up(segs.size() * sizeof(SegJob), 256);
-  const size_t ust_bytes = align_up(chain.size() * 4, 256);
-  ZT_TRY(scratch(c, 7, chain_bytes + seg_bytes + 2 * ust_bytes, &d_chain));
-  ZT_TRY(scratch(c, 3, (desc_total + 1024) * 2, &d_desc));  // + slack: chunked descriptor reads
-  ChainUnit *d_cu = static_cast<ChainUnit *>(d_chain);
-  SegJob *d_sj = reinterpret_cast<SegJob *>(static_cast<uint8_t *>(d_chain) + chain_bytes);
-  int32_t *d_ust = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(d_chain) + chain_bytes + seg_bytes);
-  int32_t *d_st = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(d_chain) + chain_bytes + seg_bytes + ust_bytes);
-  ZT_HIP(hipMemcpyAsync(d_cu, chain.data(), chain.size() * sizeof(ChainUnit), hipMemcpyHostToDevice, s));
-  ZT_HIP(hipMemcpyAsync(d_sj, segs.data(), segs.size() * sizeof(SegJob), hipMemcpyHostToDevice, s));
-  ResolveParams rp;
-  rp.tokens = static_cast<const uint32_t *>(d_tok);
-  rp.units = d_cu;
-  rp.segs = d_sj;
-  rp.out = static_cast<uint8_t *>(d_out);
-  rp.desc = static_cast<uint16_t *>(d_desc);
-  rp.unit_status = d_ust;
-  rp.seg_status = d_st;
-  rp.nunits = (uint32_t)chain.size();
-  rp.nseg = (uint32_t)segs.size();
-  rp.marker = 0;
-  rp.in = d_in;
-  ZT_TRY(resolve_segments_dev(rp, s));
+  void *d_out;
+  ZT_TRY(scratch(c, kOut, out_total, &d_out));
+  ChainRun run;
+  ZT_TRY(resolve_chain_dev(c, chain, segs, bc.desc_total, static_cast<const uint32_t *>(d_tok),
+                           static_cast<uint8_t *>(d_out), 0, d_in, 0, &run, s));
   // (sums: CRC-32 and Adler-32 of every output where it lies in d_out, behind
   // the resolve on the same stream; they come back with the statuses)
   std::vector<uint32_t> hsums;
@@ -173,16 +158,14 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
       cl[j] = chain[j].out_len;
     }
     void *d_sums;
-    ZT_TRY(scratch(c, 18, 8 * chain.size(), &d_sums));
+    ZT_TRY(scratch(c, kSums, 8 * chain.size(), &d_sums));
     ZT_TRY(checksums_batch_dev(c, static_cast<const uint8_t *>(d_out), chain.size(), co.data(), cl.data(),
                                static_cast<uint32_t *>(d_sums), s));
     hsums.resize(2 * chain.size());
     ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * chain.size(), hipMemcpyDeviceToHost, s));
   }
-  std::vector<int32_t> ust(chain.size()), sst(segs.size());
-  ZT_HIP(hipMemcpyAsync(ust.data(), d_ust, chain.size() * 4, hipMemcpyDeviceToHost, s));
-  ZT_HIP(hipMemcpyAsync(sst.data(), d_st, segs.size() * 4, hipMemcpyDeviceToHost, s));
-  ZT_HIP(hipStreamSynchronize(s));
+  ZT_TRY(chain_statuses(run, s));
+  const int32_t *ust = run.host.unit_status, *sst = run.host.seg_status;
   BT("resolve done");
   std::vector<size_t> done;
   for (size_t j = 0; j < chain.size(); ++j)
@@ -221,11 +204,7 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
   return ZT_OK;
 }
 
-// Decode `count` device-resident streams (stream i at d_in + in_off[i],
-// n[i] bytes, from index[i]); outputs are malloc'd.
-int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
-                              const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
-                              int *status);
+// The batch decoder behind inflate_batch_dev_streams / _ex (zt_internal.h)
 // (d_hist / hist_len: a preset dictionary's window, in front of every stream's
 // output: the one-wave decoder only, InfJob::hist.  extras: see zt_internal.h)
 static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
@@ -240,9 +219,14 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
     size_t g = 4 * (n[i] - std::min(n[i], index ? index[i] : (size_t)0));
     cap[i] = g < 65536 ? 65536 : g;
   }
-  void *d_jobs, *d_res;
-  ZT_TRY(scratch(c, 2, count * (sizeof(InfJob) + sizeof(InfResult)) + 256, &d_jobs));
-  d_res = (uint8_t *)d_jobs + align_up(count * sizeof(InfJob), 256);
+  InfJob *d_jobs = nullptr;
+  InfResult *d_res = nullptr;
+  ZT_TRY(scratch_carved(c, kSmall, [&](void *base) {
+    Carve cv(base);
+    d_jobs = cv.take<InfJob>(count);
+    d_res = cv.take<InfResult>(count);
+    return cv.bytes();
+  }));
   std::vector<InfJob> jobs(count);
   std::vector<InfResult> res(count);
   std::vector<size_t> todo;
@@ -280,7 +264,7 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
       out_total += align_up(cap[todo[k]], 256);
     }
     void *d_out;
-    ZT_TRY(scratch(c, 1, out_total, &d_out));
+    ZT_TRY(scratch(c, kOut, out_total, &d_out));
     for (size_t k = 0; k < todo.size(); ++k) {
       size_t i = todo[k];
       jobs[k] = InfJob{};
@@ -330,7 +314,7 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
         cl[j] = r[done[j]].out_len;
       }
       void *d_sums;
-      ZT_TRY(scratch(c, 18, 8 * done.size(), &d_sums));
+      ZT_TRY(scratch(c, kSums, 8 * done.size(), &d_sums));
       ZT_TRY(checksums_batch_dev(c, static_cast<const uint8_t *>(d_out), done.size(), co.data(), cl.data(),
                                  static_cast<uint32_t *>(d_sums), c->stream));
       hsums.resize(2 * done.size());
@@ -392,7 +376,7 @@ static int inflate_host_batch(const uint8_t *const *in, const size_t *n, const s
     in_total += align_up(n[i] ? n[i] : 1, 256);
   }
   void *d_in;
-  ZT_TRY(scratch(c, 0, in_total, &d_in));
+  ZT_TRY(scratch(c, kIn, in_total, &d_in));
   // inputs packed into pinned staging in chunks of about 32 MiB, each
   // chunk's upload issued as soon as it is packed: the copy engine moves
   // chunk k while the host packs chunk k + 1 (C2: pack 2.0 ms, then H2D 2.8)
@@ -434,27 +418,13 @@ int inflate_dev_member(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
       const size_t ne = std::min(n, index + w);
       uint8_t *d_out = nullptr;
       size_t ol = 0, eip = 0;
-      int seg = inflate_segments_dev(c, d_in, ne, index, &d_out, 0, &ol, &eip, s);
-      // the window cut a stream with sync points short (2): grow it, no
-      // general-path attempt (it cannot finish inside the window either)
+      const int seg = inflate_parallel_dev(c, d_in, ne, index, &d_out, 0, &ol, &eip, s);
+      // the window cut a stream with sync points short (2): grow it
       if (seg == 2 && ne < n) continue;
-      if (seg >= 1) {
-        d_out = nullptr;  // (the sync-point path may have placed an output of its own before it gave up)
-        seg = inflate_general_dev(c, d_in, ne, index, &d_out, 0, &ol, &eip, s);
-      }
       if (seg < 0) return seg;
       if (seg == 0) {
-        uint8_t *h = host_out(ol);
-        if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
-        const int rc = download(c, h, d_out, ol, s);
-        if (rc) {
-          zt_free(h);
-          return rc;
-        }
-        *out = h;
-        *out_len = ol;
         *end_ip = eip;
-        return ZT_OK;
+        return download_result(c, d_out, ol, false, out, out_len);
       }
       if (ne == n) break;
     }
@@ -513,13 +483,13 @@ static int inflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, size
   const size_t np = cut.size() - 1;
   if (np < 2) return 1;
   void *d_in;
-  ZT_TRY(scratch(c, 0, m + 64 * np + 256, &d_in));
-  // Results go to one device buffer at consecutive offsets (scratch slot 22,
+  ZT_TRY(scratch(c, kIn, m + 64 * np + 256, &d_in));
+  // Results go to one device buffer at consecutive offsets (kPipeOut,
   // 4x the input, as the host output used to be), each piece's capacity 4x
   // its input or what is left, and a piece that reports needing more is
   // decoded again with that.  Past the buffer's end (streams compressed
-  // better than 4:1) the pieces go to a ring of 3 overflow buffers (slots
-  // 23-25), piece i's once piece i - 3's bytes have left the device
+  // better than 4:1) the pieces go to a ring of 3 overflow buffers (from
+  // kPipeRing0), piece i's once piece i - 3's bytes have left the device
   // (PipeOut::drain).  The host output starts at piece 0's ratio x the
   // stream and grows the same way (pipeline_h2d_d2h), so a stream of any
   // ratio stays pipelined.
@@ -527,7 +497,7 @@ static int inflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, size
   auto d_piece = [&](size_t i) { return (uint8_t *)d_in + (cut[i] - index) + 64 * i; };
   const size_t cap = std::max<size_t>(4 * m, 64u << 20);
   void *d_big;
-  ZT_TRY(scratch(c, 22, cap, &d_big));
+  ZT_TRY(scratch(c, kPipeOut, cap, &d_big));
   size_t off = 0;      // bytes of the big buffer used
   size_t ring0 = np;   // first piece in the overflow ring
   double ratio0 = 0;   // output bytes per input byte of piece 0
@@ -557,20 +527,22 @@ static int inflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, size
             const size_t r = (i - ring0) % kRing;
             if (i - ring0 >= kRing) ZT_TRY(po.drain(i - kRing));
             void *p;
-            ZT_TRY(scratch(c, 23 + (int)r, want, &p));
+            ZT_TRY(scratch(c, kPipeRing0 + (int)r, want, &p));
             d_o = static_cast<uint8_t *>(p);
             ocap = want;  // (the capacity asked: the device chain sizes its descriptors from it)
           }
           size_t ol = 0, eip = 0;
           // a non-final piece must have a block boundary right before its
           // appended final block (the cut) -- and must end on that block
-          int seg = inflate_segments_dev(c, d_piece(i), pn, 0, &d_o, ocap, &ol, &eip, c->stream, last ? ~0ull : len);
+          // (the segment path alone first: only its capacity report is tried again)
+          int seg = inflate_parallel_dev(c, d_piece(i), pn, 0, &d_o, ocap, &ol, &eip, c->stream, last ? ~0ull : len,
+                                         /*allow_general=*/false);
           if (seg < 0 && ol > ocap && attempt == 0) {  // more output than its room: again with what it needs
             want = ol;
             continue;
           }
-          // (no sync points in the last piece: the speculative general decoder)
-          if (seg >= 1 && last) seg = inflate_general_dev(c, d_piece(i), pn, 0, &d_o, ocap, &ol, &eip, c->stream);
+          // (no sync points in the last piece: the speculative general decoder; the output is the caller's)
+          if (seg == 1 && last) seg = inflate_general_dev(c, d_piece(i), pn, 0, &d_o, ocap, &ol, &eip, c->stream);
           if (seg != 0) return seg < 0 ? seg : set_error(ZT_E_INTERNAL, "pipelined inflate: piece not decoded");
           if (!last && eip != pn) return set_error(ZT_E_INTERNAL, "pipelined inflate: a cut is not a block boundary");
           if (i == 0) ratio0 = (double)ol / (double)pn;
@@ -613,32 +585,15 @@ int zt_inflate_raw(const uint8_t *in, size_t n, size_t index, const zt_inflate_o
     if (!no_pipe && n - index >= kInfPipeMin && inflate_raw_pipelined(c, in, n, index, out, out_len, end_ip) == ZT_OK)
       return ZT_OK;
     void *d_in;
-    ZT_TRY(scratch(c, 0, n, &d_in));
+    ZT_TRY(scratch(c, kIn, n, &d_in));
     ZT_TRY(upload(c, d_in, in, n, c->stream));
     uint8_t *d_out = nullptr;
     size_t ol = 0, eip = 0;
-    int seg = inflate_segments_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
-    // no sync points: speculative parallel decode at arbitrary bit offsets
-    if (seg >= 1) {
-      // (the sync-point path may have placed an output of its own before it gave up -- a
-      // status found while resolving, a match reaching behind a restart point: with that
-      // pointer and no capacity the general path would refuse the stream)
-      d_out = nullptr;
-      seg = inflate_general_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
-    }
+    const int seg = inflate_parallel_dev(c, (const uint8_t *)d_in, n, index, &d_out, 0, &ol, &eip, c->stream);
     if (seg < 0) return seg;
     if (seg == 0) {
-      uint8_t *h = host_out(ol, true);
-      if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
-      const int rc = download(c, h, d_out, ol, c->stream);
-      if (rc) {
-        zt_free(h);
-        return rc;
-      }
-      *out = h;
-      *out_len = ol;
       if (end_ip) *end_ip = eip;
-      return ZT_OK;
+      return download_result(c, d_out, ol, true, out, out_len);
     }
   }
   int st = 0;
@@ -678,16 +633,16 @@ static int resume_impl(const uint8_t *in, size_t n, uint64_t bit_pos, const uint
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   void *d_in, *d_jobs;
   const size_t in_bytes = align_up(m, 256);
-  ZT_TRY(scratch(c, 0, in_bytes + wlen + 16, &d_in));
+  ZT_TRY(scratch(c, kIn, in_bytes + wlen + 16, &d_in));
   ZT_TRY(upload(c, d_in, in + byte, m, c->stream));
   const uint8_t *d_hist = (const uint8_t *)d_in + in_bytes;
   if (wlen) ZT_HIP(hipMemcpyAsync((void *)d_hist, window, wlen, hipMemcpyHostToDevice, c->stream));
-  ZT_TRY(scratch(c, 2, sizeof(InfJob) + sizeof(InfResult) + 256, &d_jobs));
+  ZT_TRY(scratch(c, kSmall, sizeof(InfJob) + sizeof(InfResult) + 256, &d_jobs));
   InfResult *d_res = (InfResult *)((uint8_t *)d_jobs + align_up(sizeof(InfJob), 256));
   size_t cap = std::max<size_t>(65536, m * 4);
   for (int pass = 0; pass < 2; ++pass) {
     void *d_out;
-    ZT_TRY(scratch(c, 1, cap, &d_out));
+    ZT_TRY(scratch(c, kOut, cap, &d_out));
     InfJob j{};
     j.in = (const uint8_t *)d_in;
     j.n = m;

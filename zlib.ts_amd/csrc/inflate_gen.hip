@@ -881,8 +881,6 @@ __global__ __launch_bounds__(256) void marker_resolve_kernel(const GenSeg *gs, c
   }
 }
 
-size_t al256(size_t v) { return (v + 255) & ~size_t(255); }
-
 void radix_sort64(std::vector<uint64_t> &v, uint64_t max_key) {
   std::vector<uint64_t> tmp(v.size());
   for (int sh = 0; sh < 64 && (max_key >> sh); sh += 11) {
@@ -914,7 +912,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
   const uint64_t nw = w_end - w_first;
   void *d_c;
   const size_t listb_bytes = (size_t)kMaxCandB * 8, list_bytes = (size_t)kMaxCand * 8;
-  ZT_TRY(scratch(c, 10, 256 + listb_bytes + list_bytes, &d_c));
+  ZT_TRY(scratch(c, kGenCand, 256 + listb_bytes + list_bytes, &d_c));
   uint32_t *d_cnt = static_cast<uint32_t *>(d_c);  // [0] stage B, [1] final
   uint64_t *d_listb = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_c) + 256);
   uint64_t *d_list = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_c) + 256 + listb_bytes);
@@ -1036,17 +1034,22 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     jobs[k].tok_cap = (uint32_t)cap;
     tok_total += (cap + 63) & ~uint64_t(63);
   }
-  void *d_tok, *d_meta, *d_bm;
-  ZT_TRY(scratch(c, 11, (tok_total + 256) * 4, &d_tok));
-  const size_t jobs_b = al256(units * sizeof(GenJob)), res_b = al256(units * sizeof(GenResult));
-  const size_t link_b = al256(units * sizeof(GenLink)), which_b = al256(units * 4);
-  ZT_TRY(scratch(c, 12, jobs_b + res_b + link_b + 2 * which_b, &d_meta));
-  ZT_TRY(scratch(c, 13, units * 2 * GEN_BM_WORDS * 4, &d_bm));
-  GenJob *d_jobs = static_cast<GenJob *>(d_meta);
-  GenResult *d_res = reinterpret_cast<GenResult *>(static_cast<uint8_t *>(d_meta) + jobs_b);
-  GenLink *d_link = reinterpret_cast<GenLink *>(static_cast<uint8_t *>(d_meta) + jobs_b + res_b);
-  uint32_t *d_which = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_meta) + jobs_b + res_b + link_b);
-  uint32_t *d_lwhich = d_which + which_b / 4;
+  void *d_tok, *d_bm;
+  ZT_TRY(scratch(c, kGenTokens, (tok_total + 256) * 4, &d_tok));
+  GenJob *d_jobs = nullptr;
+  GenResult *d_res = nullptr;
+  GenLink *d_link = nullptr;
+  uint32_t *d_which = nullptr, *d_lwhich = nullptr;
+  ZT_TRY(scratch_carved(c, kGenMeta, [&](void *base) {
+    Carve cv(base);
+    d_jobs = cv.take<GenJob>(units);
+    d_res = cv.take<GenResult>(units);
+    d_link = cv.take<GenLink>(units);
+    d_which = cv.take<uint32_t>(units);
+    d_lwhich = cv.take<uint32_t>(units);
+    return cv.bytes();
+  }));
+  ZT_TRY(scratch(c, kGenBitmap, units * 2 * GEN_BM_WORDS * 4, &d_bm));
   GenParams gp;
   gp.in = d_in;
   gp.n = n;
@@ -1221,7 +1224,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     if (segs.empty() || total - seg_start >= kSeg) {
       if (!segs.empty()) {
         gsegs.back().len = total - seg_start;
-        base16 += al256(total - seg_start);
+        base16 += align_up(total - seg_start, 256);
       }
       desc_total = (desc_total + 511) & ~uint64_t(511);
       desc_seg = desc_total;
@@ -1236,7 +1239,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     desc_total = desc_seg + (total - seg_start);
   }
   gsegs.back().len = total - seg_start;
-  base16 += al256(total - seg_start);
+  base16 += align_up(total - seg_start, 256);
   if (gen_debug()) {
     fprintf(stderr, "[zt inflate gen] chain %zu units, %zu segments of ~%llu B, output %llu B\n", chain.size(),
             gsegs.size(), (unsigned long long)kSeg, (unsigned long long)total);
@@ -1273,7 +1276,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
   uint8_t *d_out = *d_out_io;
   if (!d_out) {
     void *p;
-    ZT_TRY(scratch(c, 1, total ? total : 1, &p));
+    ZT_TRY(scratch(c, kOut, total ? total : 1, &p));
     d_out = static_cast<uint8_t *>(p);
     *d_out_io = d_out;
   } else if (total > out_cap) {
@@ -1284,36 +1287,26 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     return ZT_OK;
   }
   // ---- 4. expand, copy with markers, windows, final bytes
-  void *d_chain, *d_desc, *d_o16, *d_win;
-  const size_t chain_bytes = al256(chain.size() * sizeof(ChainUnit));
-  const size_t seg_bytes = al256(segs.size() * sizeof(SegJob));
-  const size_t gseg_bytes = al256(gsegs.size() * sizeof(GenSeg));
-  const size_t ust_bytes = al256(chain.size() * 4);
-  ZT_TRY(scratch(c, 14, chain_bytes + seg_bytes + gseg_bytes + ust_bytes + al256(segs.size() * 4), &d_chain));
-  ZT_TRY(scratch(c, 15, (desc_total + 1024) * 2, &d_desc));
-  ZT_TRY(scratch(c, 16, (base16 + 256) * 2, &d_o16));
-  ZT_TRY(scratch(c, 17, gsegs.size() * (size_t)RING, &d_win));
-  uint8_t *cb = static_cast<uint8_t *>(d_chain);
-  ChainUnit *d_cu = reinterpret_cast<ChainUnit *>(cb);
-  SegJob *d_sj = reinterpret_cast<SegJob *>(cb + chain_bytes);
-  GenSeg *d_gs = reinterpret_cast<GenSeg *>(cb + chain_bytes + seg_bytes);
-  int32_t *d_ust = reinterpret_cast<int32_t *>(cb + chain_bytes + seg_bytes + gseg_bytes);
-  int32_t *d_st = reinterpret_cast<int32_t *>(cb + chain_bytes + seg_bytes + gseg_bytes + ust_bytes);
-  ZT_HIP(hipMemcpyAsync(d_cu, chain.data(), chain.size() * sizeof(ChainUnit), hipMemcpyHostToDevice, s));
-  ZT_HIP(hipMemcpyAsync(d_sj, segs.data(), segs.size() * sizeof(SegJob), hipMemcpyHostToDevice, s));
-  ZT_HIP(hipMemcpyAsync(d_gs, gsegs.data(), gsegs.size() * sizeof(GenSeg), hipMemcpyHostToDevice, s));
-  ResolveParams rp;
-  rp.tokens = gp.tokens;
-  rp.units = d_cu;
-  rp.segs = d_sj;
-  rp.out = d_out;
-  rp.desc = static_cast<uint16_t *>(d_desc);
-  rp.unit_status = d_ust;
-  rp.seg_status = d_st;
-  rp.nunits = (uint32_t)chain.size();
-  rp.nseg = (uint32_t)segs.size();
-  rp.marker = 1;
-  rp.in = nullptr;  // (the general tokenizer writes no run tokens)
+  void *d_desc, *d_o16, *d_win;
+  ZT_TRY(scratch(c, kGenDesc, (desc_total + 1024) * 2, &d_desc));
+  ZT_TRY(scratch(c, kGenOut16, (base16 + 256) * 2, &d_o16));
+  ZT_TRY(scratch(c, kGenWindows, gsegs.size() * (size_t)RING, &d_win));
+  // The chain buffer with the GenSeg table as its extra piece.  This path
+  // shares the carve and the ResolveParams fill with the other two and keeps
+  // its own transfers: through pinned kPinInflateMeta, as resolve_chain_dev
+  // goes, zlib level-6 streams measured 0.3-1 % slower (profiles/inflate_driver_ab.txt)
+  void *d_chain;
+  const size_t gseg_bytes = gsegs.size() * sizeof(GenSeg);
+  ZT_TRY(scratch(c, kGenChain, chain_buf(nullptr, chain.size(), segs.size(), gseg_bytes).bytes, &d_chain));
+  ChainRun run{chain_buf(d_chain, chain.size(), segs.size(), gseg_bytes), ChainBuf{}, (uint32_t)chain.size(),
+               (uint32_t)segs.size()};
+  GenSeg *d_gs = reinterpret_cast<GenSeg *>(run.dev.extra);
+  ZT_HIP(hipMemcpyAsync(run.dev.units, chain.data(), chain.size() * sizeof(ChainUnit), hipMemcpyHostToDevice, s));
+  ZT_HIP(hipMemcpyAsync(run.dev.segs, segs.data(), segs.size() * sizeof(SegJob), hipMemcpyHostToDevice, s));
+  ZT_HIP(hipMemcpyAsync(d_gs, gsegs.data(), gseg_bytes, hipMemcpyHostToDevice, s));
+  int32_t *d_st = run.dev.seg_status;
+  // (in = null: the general tokenizer writes no run tokens)
+  const ResolveParams rp = resolve_params(run, gp.tokens, static_cast<uint16_t *>(d_desc), d_out, 1, nullptr);
   ZT_TRY(expand_units_dev(rp, s));
   uint16_t *o16 = static_cast<uint16_t *>(d_o16);
   copy_marker_kernel<<<rp.nseg, 64, 0, s>>>(rp, d_gs, o16);
@@ -1323,7 +1316,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     const uint32_t nwin = (uint32_t)gsegs.size() - 1;
     static const bool serial = getenv("ZT_GEN_WCHAIN") != nullptr;  // (A/B: the serial window chain)
     void *d_wj = nullptr;
-    if (!serial && nwin < WJ_MAXWIN && scratch(c, 26, 2 * (size_t)nwin * RING * 4, &d_wj) == ZT_OK) {
+    if (!serial && nwin < WJ_MAXWIN && scratch(c, kGenJump, 2 * (size_t)nwin * RING * 4, &d_wj) == ZT_OK) {
       uint32_t *e0 = static_cast<uint32_t *>(d_wj), *e1 = e0 + (size_t)nwin * RING;
       const uint32_t grid = (uint32_t)(((uint64_t)nwin * RING / 4 + 255) / 256);
       wj_init_kernel<<<grid, 256, 0, s>>>(d_gs, nwin, o16, e0);
@@ -1351,7 +1344,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
   {
     void *mb;
     ZT_TRY(mailbox(c, (chain.size() + segs.size()) * 4, &mb));
-    ZT_TRY(x_copy(mb, d_ust, chain.size() * 4, s));
+    ZT_TRY(x_copy(mb, run.dev.unit_status, chain.size() * 4, s));
     ZT_TRY(x_copy((uint8_t *)mb + chain.size() * 4, d_st, segs.size() * 4, s));
     ZT_HIP(hipStreamSynchronize(s));
     memcpy(ust.data(), mb, chain.size() * 4);

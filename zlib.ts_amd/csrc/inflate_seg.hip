@@ -25,7 +25,6 @@
 // stream with one wave (inflate.hip), which also yields the reference's
 // exact error.  Results are identical to the sequential decode by
 // construction.  Replaces src/RawInflate.ts:127-143 for such streams.
-#include <chrono>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -244,8 +243,6 @@ __global__ __launch_bounds__(256) void fs_gather(const uint64_t *__restrict__ li
   const uint64_t *src = list + (uint64_t)r * kFsRegion;
   for (uint32_t i = threadIdx.x; i < c; i += 256) out[s_off + i] = src[i];
 }
-
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
 
 // sorted candidates (pos << 1 | restart) -> first of each position
 __global__ __launch_bounds__(256) void unit_flags(const uint64_t *__restrict__ key, uint32_t cnt,
@@ -571,14 +568,7 @@ __global__ __launch_bounds__(CH_T) void chain_kernel(const TokResult *__restrict
 }
 
 // ZT_INF_TIMING=1: host wall time of inflate_segments_dev's stages on stderr (measurement only)
-static double it_now() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-#define IT(label)                                                   \
-  do {                                                              \
-    static const bool on_ = getenv("ZT_INF_TIMING") != nullptr;     \
-    if (on_) fprintf(stderr, "[inflate] %-24s %9.3f ms\n", label, it_now()); \
-  } while (0)
+#define IT(label) ZT_STAMP("ZT_INF_TIMING", "inflate", label)
 
 // a unit of the chain starts at byte `pos` (the device chain: every unit is
 // on it); flag[0] |= 1 then
@@ -587,29 +577,68 @@ __global__ void unit_starts_at(const TokJob *__restrict__ jobs, uint32_t units, 
     if (jobs[u].start == pos) atomicOr(flag, 1u);
 }
 
-int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
-                         size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary) {
-  IT("start");
-  if (n < index + (1u << 14)) return 1;  // small: one wave is as fast
+namespace {
+
+// room behind a device chain's statuses: its ChainInfo and the boundary flag
+constexpr size_t kChainTail = 512;
+static_assert(sizeof(ChainInfo) + 4 <= kChainTail, "tail holds the chain summary and the flag");
+
+// ZT_TOK_DUMP=u: unit whose first SIMT block dumps its lane state (with ZT_TOK_CHECK)
+uint32_t tok_dump_unit() { return getenv("ZT_TOK_DUMP") ? (uint32_t)atoi(getenv("ZT_TOK_DUMP")) : 0xFFFFFFFFu; }
+
+// ---- inflate_segments_dev's stages -----------------------------------------------
+// steps 1-2: the sync points found, sorted, deduplicated and turned into units
+struct SegUnits {
+  size_t units_max;   // candidates + 1: what the tables are sized for
+  size_t units;       // distinct sync points + 1
+  uint32_t nsync;     // distinct sync points
+  uint32_t nrestart;  // of them, restart points
+  uint64_t tok_total; // token slots of all units
+  uint64_t *d_off;    // [units] token offsets (kSyncSort)
+  // kTokMeta
+  uint64_t *d_stops;
+  uint8_t *d_restart;
+  TokJob *d_jobs;
+  TokResult *d_res;
+  // kTokOrder: [span keys | unit ids | sorted keys | sorted ids | sort storage]
+  bool lpt;  // launch order: longest first
+  uint32_t *d_skey, *d_uid, *d_skey2, *d_order;
+  void *d_ordtmp;
+  size_t t_ord;
+  int sort_order(hipStream_t s) const {  // d_order = unit ids by d_skey
+    size_t t = t_ord;
+    if (lpt && units > 1)
+      ZT_HIP(rocprim::radix_sort_pairs(d_ordtmp, t, d_skey, d_skey2, d_uid, d_order, units, 0u, 20u, s));
+    return ZT_OK;
+  }
+  const uint32_t *order() const { return lpt && units > 1 ? d_order : nullptr; }
+};
+
+int seg_find_units(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, hipStream_t s, SegUnits *U) {
   // 1. sync points
-  void *d_cand;
   // [counters: FS_SPLIT lines | total][regions: kMaxSync][packed: kMaxSync]
-  constexpr size_t kCntBytes = (size_t)FS_SPLIT * kFsCountStride * 4 + 256;
-  ZT_TRY(scratch(c, 5, kCntBytes + 2 * (size_t)kMaxSync * 8, &d_cand));
-  uint32_t *d_rcount = static_cast<uint32_t *>(d_cand);
-  uint32_t *d_count = d_rcount + (size_t)FS_SPLIT * kFsCountStride;
-  uint64_t *d_regions = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_cand) + kCntBytes);
-  uint64_t *d_list = d_regions + kMaxSync;
-  ZT_HIP(hipMemsetAsync(d_rcount, 0, (size_t)FS_SPLIT * kFsCountStride * 4, s));
+  struct {
+    uint32_t *rcount, *count;
+    uint64_t *regions, *list;
+  } C = {};
+  ZT_TRY(scratch_carved(c, kSyncCand, [&](void *base) {
+    Carve cv(base);
+    C.rcount = cv.take<uint32_t>((size_t)FS_SPLIT * kFsCountStride + 64);  // (+ the total's own 256 bytes)
+    C.regions = cv.take<uint64_t>(kMaxSync);
+    C.list = cv.take<uint64_t>(kMaxSync);
+    return cv.bytes();
+  }));
+  C.count = C.rcount + (size_t)FS_SPLIT * kFsCountStride;
+  ZT_HIP(hipMemsetAsync(C.rcount, 0, (size_t)FS_SPLIT * kFsCountStride * 4, s));
   const uint64_t span = n - (index & ~size_t(15));
   const uint32_t grid = (uint32_t)((span + 16 * 256 * FS_ITER - 1) / (16 * 256 * FS_ITER));
   ZT_TRY(timing_begin(c, s, 2));
-  find_syncs<<<grid, 256, 0, s>>>(d_in, index, n, d_regions, d_rcount);
+  find_syncs<<<grid, 256, 0, s>>>(d_in, index, n, C.regions, C.rcount);
   ZT_HIP(hipGetLastError());
-  fs_gather<<<FS_SPLIT, 256, 0, s>>>(d_regions, d_rcount, d_list, d_count);
+  fs_gather<<<FS_SPLIT, 256, 0, s>>>(C.regions, C.rcount, C.list, C.count);
   ZT_HIP(hipGetLastError());
   uint32_t cnt = 0;
-  ZT_TRY(readback(c, &cnt, d_count, 4, s));
+  ZT_TRY(readback(c, &cnt, C.count, 4, s));
   IT("sync points counted");
   if (cnt == 0 || cnt > kMaxSync) FALLBACK("%u sync points\n", cnt);
   // 2. the candidates sorted, deduplicated and turned into units on the
@@ -617,7 +646,7 @@ int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t ind
   // at the k-th sync point
   int end_bit = 1;
   while (end_bit < 64 && ((uint64_t)n << 1 | 1) >> end_bit) ++end_bit;
-  const size_t units_max = (size_t)cnt + 1;
+  const size_t units_max = U->units_max = (size_t)cnt + 1;
   size_t t_sort = 0, t_scan = 0, t_scan64 = 0;
   ZT_HIP(rocprim::radix_sort_keys(nullptr, t_sort, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)cnt, 0u,
                                   (unsigned)end_bit, s));
@@ -625,380 +654,396 @@ int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t ind
                                  rocprim::plus<uint32_t>(), s));
   ZT_HIP(rocprim::exclusive_scan(nullptr, t_scan64, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0,
                                  units_max, rocprim::plus<uint64_t>(), s));
-  const size_t t_bytes = align256(std::max(t_sort, std::max(t_scan, t_scan64)));
-  const size_t key_bytes = align256((size_t)cnt * 8), flag_bytes = align256(units_max * 4);
-  const size_t slot_bytes = align256(units_max * 8);
-  void *d_sort;
-  ZT_TRY(scratch(c, 20, t_bytes + key_bytes + 2 * flag_bytes + 2 * slot_bytes + 256, &d_sort));
-  uint8_t *sb = static_cast<uint8_t *>(d_sort);
-  uint64_t *d_key = reinterpret_cast<uint64_t *>(sb + t_bytes);
-  uint32_t *d_flag = reinterpret_cast<uint32_t *>(sb + t_bytes + key_bytes);
-  uint32_t *d_pos = reinterpret_cast<uint32_t *>(sb + t_bytes + key_bytes + flag_bytes);
-  uint64_t *d_slot = reinterpret_cast<uint64_t *>(sb + t_bytes + key_bytes + 2 * flag_bytes);
-  uint64_t *d_off = d_slot + slot_bytes / 8;
-  uint64_t *d_ttot = d_off + slot_bytes / 8;  // [0] token slots in all, [1] distinct sync points
-  ZT_HIP(rocprim::radix_sort_keys(sb, t_sort, d_list, d_key, (size_t)cnt, 0u, (unsigned)end_bit, s));
+  // kSyncSort: [rocPRIM storage | sorted keys | first-of-position flags |
+  // their scan | slot sizes | token offsets | totals]
+  uint8_t *sb = nullptr;
+  uint64_t *d_key = nullptr, *d_slot = nullptr, *d_ttot = nullptr;
+  uint32_t *d_flag = nullptr, *d_pos = nullptr;
+  ZT_TRY(scratch_carved(c, kSyncSort, [&](void *base) {
+    Carve cv(base);
+    sb = cv.take<uint8_t>(std::max(t_sort, std::max(t_scan, t_scan64)));
+    d_key = cv.take<uint64_t>(cnt);
+    d_flag = cv.take<uint32_t>(units_max);
+    d_pos = cv.take<uint32_t>(units_max);
+    d_slot = cv.take<uint64_t>(units_max);
+    U->d_off = cv.take<uint64_t>(units_max);
+    d_ttot = cv.take<uint64_t>(3);  // [0] token slots in all, [1] (unused), [2] restart points (u32)
+    return cv.bytes();
+  }));
+  ZT_HIP(rocprim::radix_sort_keys(sb, t_sort, C.list, d_key, (size_t)cnt, 0u, (unsigned)end_bit, s));
   const uint32_t g = (cnt + 1 + 255) / 256;
   unit_flags<<<g, 256, 0, s>>>(d_key, cnt, d_flag);
   ZT_HIP(hipGetLastError());
   ZT_HIP(rocprim::exclusive_scan(sb, t_scan, d_flag, d_pos, 0u, units_max, rocprim::plus<uint32_t>(), s));
-  const size_t stops_bytes = align256((size_t)cnt * 8);
-  const size_t restart_bytes = align256(units_max);
-  const size_t jobs_bytes = align256(units_max * sizeof(TokJob));
-  const size_t res_bytes = align256(units_max * sizeof(TokResult));
-  void *d_meta;
-  ZT_TRY(scratch(c, 6, stops_bytes + restart_bytes + jobs_bytes + res_bytes, &d_meta));
-  uint64_t *d_stops = static_cast<uint64_t *>(d_meta);
-  uint8_t *d_restart = static_cast<uint8_t *>(d_meta) + stops_bytes;
-  TokJob *d_jobs = reinterpret_cast<TokJob *>(static_cast<uint8_t *>(d_meta) + stops_bytes + restart_bytes);
-  TokResult *d_res =
-      reinterpret_cast<TokResult *>(static_cast<uint8_t *>(d_meta) + stops_bytes + restart_bytes + jobs_bytes);
+  ZT_TRY(scratch_carved(c, kTokMeta, [&](void *base) {
+    Carve cv(base);
+    U->d_stops = cv.take<uint64_t>(cnt);
+    U->d_restart = cv.take<uint8_t>(units_max);
+    U->d_jobs = cv.take<TokJob>(units_max);
+    U->d_res = cv.take<TokResult>(units_max);
+    return cv.bytes();
+  }));
   ZT_HIP(hipMemsetAsync(d_slot, 0, units_max * 8, s));
   ZT_HIP(hipMemsetAsync(d_ttot + 2, 0, 8, s));
-  // tokenize launch order (slot 28): [span keys | unit ids | sorted keys |
-  // sorted ids | sort storage]
+  // tokenize launch order (kTokOrder)
   // (up to 128 K candidates: 4 GiB of 32 KiB blocks; a crafted stream of
   // dense false candidates keeps the position order and no order buffers)
   static const bool lpt_env = getenv("ZT_TOK_ORDER") ? atoi(getenv("ZT_TOK_ORDER")) != 0 : true;
-  const bool lpt = lpt_env && units_max <= (1u << 17);
-  size_t t_ord = 0;
-  if (lpt)
-    ZT_HIP(rocprim::radix_sort_pairs(nullptr, t_ord, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+  U->lpt = lpt_env && units_max <= (1u << 17);
+  U->t_ord = 0;
+  if (U->lpt)
+    ZT_HIP(rocprim::radix_sort_pairs(nullptr, U->t_ord, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                      (const uint32_t *)nullptr, (uint32_t *)nullptr, units_max, 0u, 20u, s));
-  const size_t ord_b = align256((lpt ? units_max : 1) * 4);
-  void *d_ordbuf;
-  ZT_TRY(scratch(c, 28, 4 * ord_b + align256(t_ord), &d_ordbuf));
-  uint32_t *d_skey = static_cast<uint32_t *>(d_ordbuf);
-  uint32_t *d_uid = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_ordbuf) + ord_b);
-  uint32_t *d_skey2 = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_ordbuf) + 2 * ord_b);
-  uint32_t *d_order = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(d_ordbuf) + 3 * ord_b);
-  void *d_ordtmp = static_cast<uint8_t *>(d_ordbuf) + 4 * ord_b;
-  unit_jobs<<<g, 256, 0, s>>>(d_key, d_flag, d_pos, cnt, n, index, kUnitTokCap, d_stops, d_restart, d_jobs, d_slot,
-                              reinterpret_cast<uint32_t *>(d_ttot + 2), lpt ? d_skey : nullptr, d_uid);
+  ZT_TRY(scratch_carved(c, kTokOrder, [&](void *base) {
+    Carve cv(base);
+    const size_t k = U->lpt ? units_max : 1;
+    U->d_skey = cv.take<uint32_t>(k);
+    U->d_uid = cv.take<uint32_t>(k);
+    U->d_skey2 = cv.take<uint32_t>(k);
+    U->d_order = cv.take<uint32_t>(k);
+    U->d_ordtmp = cv.take<uint8_t>(U->t_ord);
+    return cv.bytes();
+  }));
+  unit_jobs<<<g, 256, 0, s>>>(d_key, d_flag, d_pos, cnt, n, index, kUnitTokCap, U->d_stops, U->d_restart, U->d_jobs,
+                              d_slot, reinterpret_cast<uint32_t *>(d_ttot + 2), U->lpt ? U->d_skey : nullptr, U->d_uid);
   ZT_HIP(hipGetLastError());
-  ZT_HIP(rocprim::exclusive_scan(sb, t_scan64, d_slot, d_off, (uint64_t)0, units_max, rocprim::plus<uint64_t>(), s));
-  unit_slots<<<g, 256, 0, s>>>(d_off, d_slot, d_pos + cnt, d_jobs, d_ttot);
+  ZT_HIP(rocprim::exclusive_scan(sb, t_scan64, d_slot, U->d_off, (uint64_t)0, units_max, rocprim::plus<uint64_t>(), s));
+  unit_slots<<<g, 256, 0, s>>>(U->d_off, d_slot, d_pos + cnt, U->d_jobs, d_ttot);
   ZT_HIP(hipGetLastError());
-  uint64_t tot_h[3] = {0, 0, 0};
-  {
-    void *mb;
-    ZT_TRY(mailbox(c, 24, &mb));
-    uint64_t *m64 = static_cast<uint64_t *>(mb);
-    m64[1] = m64[2] = 0;
-    ZT_TRY(x_copy(&m64[0], d_ttot, 8, s));
-    ZT_TRY(x_copy(&m64[1], d_pos + cnt, 4, s));
-    ZT_TRY(x_copy(&m64[2], d_ttot + 2, 4, s));
-    ZT_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < 3; ++k) tot_h[k] = m64[k];
-  }
+  void *mb;
+  ZT_TRY(mailbox(c, 24, &mb));
+  uint64_t *m64 = static_cast<uint64_t *>(mb);
+  m64[1] = m64[2] = 0;
+  ZT_TRY(x_copy(&m64[0], d_ttot, 8, s));
+  ZT_TRY(x_copy(&m64[1], d_pos + cnt, 4, s));
+  ZT_TRY(x_copy(&m64[2], d_ttot + 2, 4, s));
+  ZT_HIP(hipStreamSynchronize(s));
   IT("units counted");
-  const uint32_t nsync = (uint32_t)tot_h[1];
-  const size_t units = (size_t)nsync + 1;
+  U->tok_total = m64[0];
+  U->nsync = (uint32_t)m64[1];
+  U->nrestart = (uint32_t)m64[2];
+  U->units = (size_t)U->nsync + 1;
+  return ZT_OK;
+}
+
+// the unit tables in pinned staging (kPinInflateMeta), sized for the chain
+// buffer's mirror behind them (chain_upload, the device chain's readback)
+struct SegPinned {
+  uint8_t *restart;
+  TokResult *res;
+  uint64_t *tok_off;
+  size_t front;  // bytes of the three tables
+  size_t bytes;
+};
+SegPinned seg_pinned(void *base, size_t units_max) {
+  Carve cv(base);
+  SegPinned P;
+  P.restart = cv.take<uint8_t>(units_max);
+  P.res = cv.take<TokResult>(units_max);
+  P.tok_off = cv.take<uint64_t>(units_max);
+  P.front = cv.bytes();
+  P.bytes = P.front + chain_buf(nullptr, units_max, units_max, 0, kChainTail).bytes;
+  return P;
+}
+
+// tokenize: the token slots, the launch order, the kernel
+int seg_tokenize(DeviceCtx *c, const uint8_t *d_in, size_t n, const SegUnits &U, hipStream_t s, uint32_t **d_tok_out,
+                 SegPinned *pin, uint64_t **dbg) {
   // Every candidate sync point gets a token slot before the chain shows which
   // are real block boundaries; the slots are bounded by the input bits up to
   // the next candidate (unit_jobs), so all of them together stay below 8
   // tokens per input byte + 64 per candidate.  Past the device's free memory,
   // or when the slots cannot be allocated, the stream takes the general path.
-  const size_t tok_bytes = ((size_t)tot_h[0] + 256) * 4;  // + slack: chunked token reads
+  const size_t tok_bytes = ((size_t)U.tok_total + 256) * 4;  // + slack: chunked token reads
   // (only asked when the cached slots are too small: hipMemGetInfo is a
   // driver round trip on every call otherwise)
-  if (tok_bytes > c->buf_size[4]) {
+  if (tok_bytes > c->buf_size[kTokens]) {
     size_t mem_free = 0, mem_total = 0;
     ZT_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    if (tok_bytes > c->buf_size[4] + mem_free / 2) FALLBACK("%zu sync candidates: token slots over budget\n", units);
+    if (tok_bytes > c->buf_size[kTokens] + mem_free / 2)
+      FALLBACK("%zu sync candidates: token slots over budget\n", U.units);
   }
-  void *d_tok;
-  if (scratch(c, 4, tok_bytes, &d_tok) != ZT_OK) FALLBACK("token slots (%zu B) not allocated\n", tok_bytes);
-  // metadata comes back through pinned staging (slot 1):
-  // [restart flags | results | token offsets | chain | segments | statuses]
-  void *hp;
-  const size_t meta_a = restart_bytes + res_bytes + slot_bytes;
-  const size_t meta_b = align256(units_max * sizeof(ChainUnit)) + align256(units_max * sizeof(SegJob)) +
-                        2 * align256(units_max * 4);
-  ZT_TRY(pinned(c, meta_a + meta_b, &hp, 1));
-  uint8_t *pin = static_cast<uint8_t *>(hp);
-  const uint8_t *restart = pin;
+  void *d_tok, *hp;
+  if (scratch(c, kTokens, tok_bytes, &d_tok) != ZT_OK) FALLBACK("token slots (%zu B) not allocated\n", tok_bytes);
+  // metadata comes back through pinned staging
+  ZT_TRY(pinned(c, seg_pinned(nullptr, U.units_max).bytes, &hp, kPinInflateMeta));
+  *pin = seg_pinned(hp, U.units_max);
   // longest units first: the kernel's last units are short ones, so its tail
   // (SIMDs idle while the last units finish) is short
-  if (lpt && units > 1)
-    ZT_HIP(rocprim::radix_sort_pairs(d_ordtmp, t_ord, d_skey, d_skey2, d_uid, d_order, units, 0u, 20u, s));
+  ZT_TRY(U.sort_order(s));
   TokParams tp;
   tp.in = d_in;
   tp.n = n;
-  tp.order = lpt && units > 1 ? d_order : nullptr;
-  tp.stops = d_stops;
-  tp.nstops = nsync;
-  tp.jobs = d_jobs;
-  tp.res = d_res;
-  tp.tokens = static_cast<uint32_t *>(d_tok);
-  tp.count = (uint32_t)units;
-  static const char *simt_env = getenv("ZT_TOK_SIMT");
-  tp.simt = simt_env ? atoi(simt_env) != 0 : 1;
-  const bool check = getenv("ZT_TOK_CHECK") != nullptr;
+  tp.order = U.order();
+  tp.stops = U.d_stops;
+  tp.nstops = U.nsync;
+  tp.jobs = U.d_jobs;
+  tp.res = U.d_res;
+  tp.tokens = *d_tok_out = static_cast<uint32_t *>(d_tok);
+  tp.count = (uint32_t)U.units;
+  tp.simt = tok_simt_env();
   tp.dbg = nullptr;
-  if (check) {
+  if (getenv("ZT_TOK_CHECK")) {
     void *d_dbg;
-    ZT_TRY(scratch(c, 2, units * 64 + 8 * 64 * 32, &d_dbg));
-    ZT_HIP(hipMemsetAsync(d_dbg, 0, units * 64 + 8 * 64 * 32, s));
+    ZT_TRY(scratch(c, kSmall, U.units * 64 + 8 * 64 * 32, &d_dbg));
+    ZT_HIP(hipMemsetAsync(d_dbg, 0, U.units * 64 + 8 * 64 * 32, s));
     tp.dbg = static_cast<uint64_t *>(d_dbg);
   }
-  tp.dump_unit = getenv("ZT_TOK_DUMP") ? (uint32_t)atoi(getenv("ZT_TOK_DUMP")) : 0xFFFFFFFFu;
+  *dbg = tp.dbg;
+  tp.dump_unit = tok_dump_unit();
   tp.dump_once = 0;
   tp.run_tokens = 1;
   ZT_TRY(timing_begin(c, s, 3));
   ZT_TRY(tokenize_units_dev(tp, s));
-  ZT_TRY(timing_end(c, s, 3));
-  // 3a. the common case: chain, segments and the resolve kernels straight on
-  // the device (a caller-owned output: its capacity bounds the descriptors);
+  return timing_end(c, s, 3);
+}
+
+// ZT_TOK_CHECK / ZT_TOK_DUMP: what the tokenizer's debug words say (after the stream is synchronized)
+int tok_check_print(const uint64_t *d_dbg, size_t units) {
+  std::vector<uint64_t> dbg(units * 8);
+  ZT_HIP(hipMemcpy(dbg.data(), d_dbg, units * 64, hipMemcpyDeviceToHost));
+  size_t bad = 0;
+  for (size_t i = 0; i < units; ++i)
+    if (dbg[i * 8]) {
+      if (bad++ < 8)
+        fprintf(stderr, "[zt tok check] unit %zu body@%llu: end simt %llu scalar %llu, tokens %llu/%llu, bytes %llu/%llu\n",
+                i, (unsigned long long)dbg[i * 8 + 1], (unsigned long long)dbg[i * 8 + 2],
+                (unsigned long long)dbg[i * 8 + 3], (unsigned long long)dbg[i * 8 + 4],
+                (unsigned long long)dbg[i * 8 + 5], (unsigned long long)dbg[i * 8 + 6],
+                (unsigned long long)dbg[i * 8 + 7]);
+    }
+  fprintf(stderr, "[zt tok check] %zu of %zu units differ\n", bad, units);
+  if (tok_dump_unit() < units) {
+    std::vector<uint32_t> dd(8 * 64 * 8);
+    ZT_HIP(hipMemcpy(dd.data(), d_dbg + units * 8, dd.size() * 4, hipMemcpyDeviceToHost));
+    for (int r = 0; r < 8; ++r) {
+      if (r > 0 && dd[(r * 64) * 8] == 0) break;
+      fprintf(stderr, "round %d R=%u last=%d\n", r, dd[(r * 64) * 8], (int)dd[(r * 64) * 8 + 6]);
+      for (int l = 0; l < 64; ++l) {
+        const uint32_t *d = &dd[(r * 64 + l) * 8];
+        fprintf(stderr, "  l%02d t=%u end=%u tok=%u e=%d fl=%u ev=%u\n", l, d[1], d[2], d[3], (int)d[4], d[5], d[7]);
+      }
+    }
+  }
+  return ZT_OK;
+}
+
+// what every stage from the chain on needs
+struct SegCall {
+  DeviceCtx *c;
+  const uint8_t *d_in;
+  size_t n;
+  uint8_t **d_out_io;
+  size_t out_cap;
+  size_t *out_len, *end_ip;
+  hipStream_t s;
+  uint64_t boundary;
+};
+
+int seg_done(const SegCall &a, const ChainRun &run, const char *tag) {
+  DeviceCtx *c = a.c;
+  ZT_TRY(timing_collect(c, &c->times.inflate_ms, &c->times.inflate_launches, 2));
+  ZT_TRY(timing_collect(c, &c->times.inflate_tok_ms, &c->times.inflate_toks, 3));
+  for (uint32_t i = 0; i < run.nunits; ++i)
+    if (run.host.unit_status[i] != ZT_OK)
+      FALLBACK("unit %u of %u (%s): status %d\n", i, run.nunits, tag, run.host.unit_status[i]);
+  for (uint32_t i = 0; i < run.nseg; ++i)
+    if (run.host.seg_status[i] != ZT_OK) FALLBACK("segment %u of %u: status %d\n", i, run.nseg, run.host.seg_status[i]);
+  c->times.inflate_paths[0]++;
+  return ZT_OK;
+}
+
+// 3a. the common case: chain, segments and the resolve kernels straight on
+// the device (a caller-owned output: its capacity bounds the descriptors).
+// *resolved: the stream is done (ZT_OK) or left this path (1); otherwise the
+// kernels did nothing and the host walks the chain.
+int seg_chain_device(const SegCall &a, const SegUnits &U, const uint32_t *d_tok, const SegPinned &pin, bool plain,
+                     bool *resolved) {
+  DeviceCtx *c = a.c;
+  hipStream_t s = a.s;
+  *resolved = false;
   // ZT_INF_HOST_CHAIN=1 forces the host walk (measurement)
   static const bool host_chain = getenv("ZT_INF_HOST_CHAIN") != nullptr;
-  const uint32_t max_seg = (uint32_t)std::min<uint64_t>(tot_h[2] + 1, units);
-  const uint64_t desc_cap = (uint64_t)out_cap + 512ull * max_seg + 2048;
+  const size_t units = U.units;
+  const uint32_t max_seg = (uint32_t)std::min<uint64_t>((uint64_t)U.nrestart + 1, units);
+  const uint64_t desc_cap = (uint64_t)a.out_cap + 512ull * max_seg + 2048;
   // The descriptors are sized from the caller's capacity here (the decoded
   // size is known only after the chain), and the scratch cache only grows: a
   // generous capacity takes the device chain only when its descriptors fit
-  // what slot 3 already holds or 8 bytes per input byte (output up to 4x the
-  // input); otherwise, and when the slot cannot grow, the host walks the chain
-  // and sizes them from the real total.
-  const bool desc_fits = desc_cap * 2 <= c->buf_size[3] || desc_cap * 2 <= 8ull * n + 4ull * (512ull * max_seg + 2048);
-  if (*d_out_io && !check && !inf_debug() && !host_chain && max_seg <= CH_MAXS && units <= CH_MAXU &&
-      out_cap <= (64ull << 30) && desc_fits) {
-    void *d_chain, *d_desc;
-    const size_t chain_bytes = align256(units * sizeof(ChainUnit)), seg_bytes = align256(max_seg * sizeof(SegJob));
-    const size_t ust_bytes = align256(units * 4), st_bytes = align256(max_seg * 4);
-    ZT_TRY(scratch(c, 7, chain_bytes + seg_bytes + ust_bytes + st_bytes + 512, &d_chain));
-    if (scratch(c, 3, desc_cap * 2, &d_desc) != ZT_OK) {
-      (void)hipGetLastError();  // (the failed allocation's sticky error)
-      goto host_walk;
-    }
-    uint8_t *cb = static_cast<uint8_t *>(d_chain);
-    ChainUnit *d_cu = reinterpret_cast<ChainUnit *>(cb);
-    SegJob *d_sj = reinterpret_cast<SegJob *>(cb + chain_bytes);
-    int32_t *d_ust = reinterpret_cast<int32_t *>(cb + chain_bytes + seg_bytes);
-    int32_t *d_st = reinterpret_cast<int32_t *>(cb + chain_bytes + seg_bytes + ust_bytes);
-    ChainInfo *d_info = reinterpret_cast<ChainInfo *>(cb + chain_bytes + seg_bytes + ust_bytes + st_bytes);
-    uint32_t *d_bflag = reinterpret_cast<uint32_t *>(d_info + 1);
-    if (boundary != ~0ull) {
-      ZT_HIP(hipMemsetAsync(d_bflag, 0, 4, s));
-      unit_starts_at<<<(uint32_t)std::min<size_t>(64, (units + 255) / 256), 256, 0, s>>>(d_jobs, (uint32_t)units,
-                                                                                        boundary, d_bflag);
-      ZT_HIP(hipGetLastError());
-    }
-    // (the tokenize order's buffers, free again, hold expand's: most tokens first)
-    chain_kernel<<<1, CH_T, 0, s>>>(d_res, d_restart, d_off, (uint32_t)units, out_cap, desc_cap, max_seg, d_cu, d_sj,
-                                    d_info, lpt ? d_skey : nullptr, d_uid);
-    ZT_HIP(hipGetLastError());
-    if (lpt && units > 1)
-      ZT_HIP(rocprim::radix_sort_pairs(d_ordtmp, t_ord, d_skey, d_skey2, d_uid, d_order, units, 0u, 20u, s));
-    ResolveParams rp;
-    rp.tokens = static_cast<const uint32_t *>(d_tok);
-    rp.units = d_cu;
-    rp.segs = d_sj;
-    rp.out = *d_out_io;
-    rp.desc = static_cast<uint16_t *>(d_desc);
-    rp.unit_status = d_ust;
-    rp.seg_status = d_st;
-    rp.nunits = (uint32_t)units;
-    rp.nseg = max_seg;  // (grid; copy waves past info->nseg return at once)
-    rp.marker = 0;
-    rp.in = d_in;
-    rp.info = d_info;
-    rp.order = lpt && units > 1 ? d_order : nullptr;
-    IT("device chain launched");
-    ZT_TRY(resolve_segments_dev(rp, s));
-    ZT_TRY(timing_end(c, s, 2));
-    // back in one copy: the chain summary and every status
-    uint8_t *hb = pin + meta_a;
-    ZT_TRY(x_copy(hb, d_ust, ust_bytes + st_bytes + sizeof(ChainInfo) + 4, s));
-    ZT_HIP(hipStreamSynchronize(s));
-    IT("resolved (device chain)");
-    const ChainInfo info = *reinterpret_cast<const ChainInfo *>(hb + ust_bytes + st_bytes);
-    if (info.ok) {
-      if (boundary != ~0ull && !*reinterpret_cast<const uint32_t *>(hb + ust_bytes + st_bytes + sizeof(ChainInfo)))
-        FALLBACK("no unit of the chain starts at the boundary %llu\n", (unsigned long long)boundary);
-      ZT_TRY(timing_collect(c, &c->times.inflate_ms, &c->times.inflate_launches, 2));
-      ZT_TRY(timing_collect(c, &c->times.inflate_tok_ms, &c->times.inflate_toks, 3));
-      const int32_t *h_ust = reinterpret_cast<const int32_t *>(hb);
-      const int32_t *h_st = reinterpret_cast<const int32_t *>(hb + ust_bytes);
-      for (size_t i = 0; i < units; ++i)
-        if (h_ust[i] != ZT_OK) FALLBACK("unit %zu of %zu (device chain): status %d\n", i, units, h_ust[i]);
-      for (size_t i = 0; i < info.nseg; ++i)
-        if (h_st[i] != ZT_OK) FALLBACK("segment %zu of %u: status %d\n", i, info.nseg, h_st[i]);
-      *out_len = info.total;
-      *end_ip = (info.end_bits + 7) >> 3;
-      c->times.inflate_paths[0]++;
-      return ZT_OK;
-    }
-    // not the common case: the host walks the chain (the kernels above did nothing)
-    ZT_TRY(timing_begin(c, s, 2));
+  // what the descriptor slot already holds or 8 bytes per input byte (output
+  // up to 4x the input); otherwise, and when the slot cannot grow, the host
+  // walks the chain and sizes them from the real total.
+  const bool desc_fits = desc_cap * 2 <= c->buf_size[kDeflateOrDesc] ||
+                         desc_cap * 2 <= 8ull * a.n + 4ull * (512ull * max_seg + 2048);
+  if (!*a.d_out_io || !plain || host_chain || max_seg > CH_MAXS || units > CH_MAXU || a.out_cap > (64ull << 30) ||
+      !desc_fits)
+    return ZT_OK;
+  void *d_chain, *d_desc;
+  ZT_TRY(scratch(c, kChain, chain_buf(nullptr, units, max_seg, 0, kChainTail).bytes, &d_chain));
+  if (scratch(c, kDeflateOrDesc, desc_cap * 2, &d_desc) != ZT_OK) {
+    (void)hipGetLastError();  // (the failed allocation's sticky error)
+    return ZT_OK;
   }
-host_walk:
-  TokResult *res = reinterpret_cast<TokResult *>(pin + restart_bytes);
-  ZT_TRY(x_copy(pin, d_restart, nsync, s));
-  ZT_TRY(x_copy(res, d_res, units * sizeof(TokResult), s));
-  const uint64_t *tok_off = reinterpret_cast<const uint64_t *>(pin + restart_bytes + res_bytes);
-  ZT_TRY(x_copy(pin + restart_bytes + res_bytes, d_off, units * 8, s));
+  ChainRun run;
+  run.dev = chain_buf(d_chain, units, max_seg, 0, kChainTail);
+  run.host = chain_buf(pin.restart + pin.front, units, max_seg, 0, kChainTail);
+  run.nunits = (uint32_t)units;
+  run.nseg = max_seg;  // (grid; copy waves past info->nseg return at once)
+  ChainInfo *d_info = reinterpret_cast<ChainInfo *>(run.dev.tail);
+  uint32_t *d_bflag = reinterpret_cast<uint32_t *>(d_info + 1);
+  if (a.boundary != ~0ull) {
+    ZT_HIP(hipMemsetAsync(d_bflag, 0, 4, s));
+    unit_starts_at<<<(uint32_t)std::min<size_t>(64, (units + 255) / 256), 256, 0, s>>>(U.d_jobs, (uint32_t)units,
+                                                                                      a.boundary, d_bflag);
+    ZT_HIP(hipGetLastError());
+  }
+  // (the tokenize order's buffers, free again, hold expand's: most tokens first)
+  chain_kernel<<<1, CH_T, 0, s>>>(U.d_res, U.d_restart, U.d_off, (uint32_t)units, a.out_cap, desc_cap, max_seg,
+                                  run.dev.units, run.dev.segs, d_info, U.lpt ? U.d_skey : nullptr, U.d_uid);
+  ZT_HIP(hipGetLastError());
+  ZT_TRY(U.sort_order(s));
+  ResolveParams rp = resolve_params(run, d_tok, static_cast<uint16_t *>(d_desc), *a.d_out_io, 0, a.d_in);
+  rp.info = d_info;
+  rp.order = U.order();
+  IT("device chain launched");
+  ZT_TRY(resolve_segments_dev(rp, s));
+  ZT_TRY(timing_end(c, s, 2));
+  // back in one copy: every status, the chain summary and the boundary flag
+  ZT_TRY(x_copy(run.host.unit_status, run.dev.unit_status,
+                (size_t)(run.dev.tail - reinterpret_cast<uint8_t *>(run.dev.unit_status)) + sizeof(ChainInfo) + 4, s));
+  ZT_HIP(hipStreamSynchronize(s));
+  IT("resolved (device chain)");
+  const ChainInfo info = *reinterpret_cast<const ChainInfo *>(run.host.tail);
+  if (!info.ok)  // not the common case: the host walks the chain (the kernels above did nothing)
+    return timing_begin(c, s, 2);
+  *resolved = true;
+  if (a.boundary != ~0ull && !*reinterpret_cast<const uint32_t *>(run.host.tail + sizeof(ChainInfo)))
+    FALLBACK("no unit of the chain starts at the boundary %llu\n", (unsigned long long)a.boundary);
+  run.nseg = info.nseg;
+  ZT_TRY(seg_done(a, run, "device chain"));
+  *a.out_len = info.total;
+  *a.end_ip = (info.end_bits + 7) >> 3;
+  return ZT_OK;
+}
+
+// 3b-4. the unit tables back to the host, the chain walked there
+// (seg_chain_host), then expand (one wave per unit) and copy (one wave per
+// segment)
+int seg_chain_on_host(const SegCall &a, const SegUnits &U, const uint32_t *d_tok, const SegPinned &pin,
+                      const uint64_t *d_dbg) {
+  DeviceCtx *c = a.c;
+  hipStream_t s = a.s;
+  const size_t units = U.units;
+  ZT_TRY(x_copy(pin.restart, U.d_restart, U.nsync, s));
+  ZT_TRY(x_copy(pin.res, U.d_res, units * sizeof(TokResult), s));
+  ZT_TRY(x_copy(pin.tok_off, U.d_off, units * 8, s));
   ZT_HIP(hipStreamSynchronize(s));
   IT("tokenized");
-  if (check) {
-    std::vector<uint64_t> dbg(units * 8);
-    ZT_HIP(hipMemcpy(dbg.data(), tp.dbg, units * 64, hipMemcpyDeviceToHost));
-    size_t bad = 0;
-    for (size_t i = 0; i < units; ++i)
-      if (dbg[i * 8]) {
-        if (bad++ < 8)
-          fprintf(stderr, "[zt tok check] unit %zu body@%llu: end simt %llu scalar %llu, tokens %llu/%llu, bytes %llu/%llu\n",
-                  i, (unsigned long long)dbg[i * 8 + 1], (unsigned long long)dbg[i * 8 + 2],
-                  (unsigned long long)dbg[i * 8 + 3], (unsigned long long)dbg[i * 8 + 4],
-                  (unsigned long long)dbg[i * 8 + 5], (unsigned long long)dbg[i * 8 + 6],
-                  (unsigned long long)dbg[i * 8 + 7]);
-      }
-    fprintf(stderr, "[zt tok check] %zu of %zu units differ\n", bad, units);
-    if (tp.dump_unit < units) {
-      std::vector<uint32_t> dd(8 * 64 * 8);
-      ZT_HIP(hipMemcpy(dd.data(), tp.dbg + units * 8, dd.size() * 4, hipMemcpyDeviceToHost));
-      for (int r = 0; r < 8; ++r) {
-        if (r > 0 && dd[(r * 64) * 8] == 0) break;
-        fprintf(stderr, "round %d R=%u last=%d\n", r, dd[(r * 64) * 8], (int)dd[(r * 64) * 8 + 6]);
-        for (int l = 0; l < 64; ++l) {
-          const uint32_t *d = &dd[(r * 64 + l) * 8];
-          fprintf(stderr, "  l%02d t=%u end=%u tok=%u e=%d fl=%u ev=%u\n", l, d[1], d[2], d[3], (int)d[4], d[5], d[7]);
-        }
-      }
-    }
+  if (d_dbg) ZT_TRY(tok_check_print(d_dbg, units));
+  const ChainPlan plan = seg_chain_host(pin.res, pin.restart, pin.tok_off, units);
+  if (plan.outcome != ChainPlan::kBuilt) {
+    if (inf_debug()) fprintf(stderr, "[zt inflate] %s", plan.why.c_str());
+    return plan.outcome == ChainPlan::kTruncated ? 2 : 1;
   }
-  // 3. the chain from the stream start, cut into segments at restart markers
-  std::vector<size_t> chained;  // (units on the chain, for the boundary check)
-  std::vector<ChainUnit> chain;
-  std::vector<SegJob> segs;
-  uint64_t total = 0, seg_start = 0, desc_total = 0, desc_seg = 0;
-  size_t u = 0;
-  for (;;) {
-    const TokResult &r = res[u];
-    // the chain reached the last unit (which runs to the end of the input)
-    // and that one ran out of input: a window that cuts a longer stream
-    // (inflate_dev_member grows it) -- or a truncated stream
-    if (u + 1 == units && u > 0 && (r.status == ZT_E_INPUT_BROKEN || r.status == ZT_E_STORED_LEN)) {
-      if (inf_debug()) fprintf(stderr, "[zt inflate] chain ran out of input in its last unit %zu\n", u);
-      return 2;
-    }
-    if (r.status != ZT_OK || r.out_len > 0xFFFFFFFFull)
-      FALLBACK("unit %zu (chain %zu): status %d detail %d ntok %u out %llu\n", u, chain.size(), r.status,
-               r.detail, r.ntok, (unsigned long long)r.out_len);
-    // (a restart point right after another -- the empty stored blocks of a
-    // restart marker -- leaves the segment before it empty: that one simply
-    // starts here instead.  Empty copy waves would sit between the full ones
-    // in the launch, and the workgroup -> XCD round robin would then give
-    // half of the XCDs every 1 MiB segment: two rounds of copy waves.)
-    const bool seg_start_here = u == 0 || restart[u - 1];
-    if (segs.empty() || (seg_start_here && total != seg_start)) {
-      desc_total = (desc_total + 511) & ~uint64_t(511);
-      desc_seg = desc_total;
-      seg_start = total;
-      segs.push_back(SegJob{(uint32_t)chain.size(), 0});
-    }
-    chain.push_back(ChainUnit{tok_off[u], total, seg_start, desc_seg + (total - seg_start), r.ntok,
-                              (uint32_t)r.out_len});
-    chained.push_back(u);
-    segs.back().count++;
-    total += r.out_len;
-    desc_total = desc_seg + (total - seg_start);
-    if (r.stop_idx < 0) break;
-    const size_t nx = (size_t)r.stop_idx + 1;
-    if (nx <= u || nx >= units) FALLBACK("unit %zu: bad stop %d\n", u, r.stop_idx);
-    u = nx;
-  }
-  // a segment of units that hold stored runs only (TokResult ntok bit 30;
-  // or nothing) is written by expand_kernel straight from the input and
-  // skipped by copy_kernel (SegJob count bit 31); elsewhere bit 30 is cleared
-  for (SegJob &sj : segs) {
-    bool direct = true;
-    for (uint32_t k = 0; k < sj.count; ++k) {
-      const ChainUnit &cu = chain[sj.first + k];
-      direct = direct && ((cu.ntok >> 30) == 3u || cu.out_len == 0);  // (empty units: the restart markers)
-    }
-    for (uint32_t k = 0; k < sj.count && !direct; ++k) chain[sj.first + k].ntok &= ~0x40000000u;
-    if (direct) sj.count |= 0x80000000u;
-  }
-  if (boundary != ~0ull) {
+  if (a.boundary != ~0ull) {
     std::vector<TokJob> hj(units);
-    ZT_TRY(readback(c, hj.data(), d_jobs, units * sizeof(TokJob), s));
+    ZT_TRY(readback(c, hj.data(), U.d_jobs, units * sizeof(TokJob), s));
     bool at = false;
-    for (size_t k : chained) at = at || hj[k].start == boundary;
-    if (!at) FALLBACK("no unit of the chain starts at the boundary %llu\n", (unsigned long long)boundary);
+    for (uint32_t k : plan.on_chain) at = at || hj[k].start == a.boundary;
+    if (!at) FALLBACK("no unit of the chain starts at the boundary %llu\n", (unsigned long long)a.boundary);
   }
-  *out_len = total;
-  *end_ip = (res[u].end_bits + 7) >> 3;
+  *a.out_len = plan.total;
+  *a.end_ip = (pin.res[plan.last].end_bits + 7) >> 3;
   if (inf_debug()) {
     // segment sizes (copy_kernel: one wave per segment)
     uint64_t mn = ~0ull, mx = 0;
     size_t small = 0;
-    for (size_t i = 0; i < segs.size(); ++i) {
-      const ChainUnit &a = chain[segs[i].first], &b = chain[segs[i].first + (segs[i].count & 0x7FFFFFFFu) - 1];
-      const uint64_t len = b.out_off + b.out_len - a.out_off;
+    for (const SegJob &sj : plan.segs) {
+      const ChainUnit &f = plan.chain[sj.first], &b = plan.chain[sj.first + (sj.count & 0x7FFFFFFFu) - 1];
+      const uint64_t len = b.out_off + b.out_len - f.out_off;
       mn = len < mn ? len : mn;
       mx = len > mx ? len : mx;
       small += len < (512u << 10);
     }
     fprintf(stderr, "[zt inflate] %zu units, %zu segments, %llu bytes: segment min %llu max %llu, %zu under 512 KiB\n",
-            chain.size(), segs.size(), (unsigned long long)total, (unsigned long long)mn, (unsigned long long)mx, small);
+            plan.chain.size(), plan.segs.size(), (unsigned long long)plan.total, (unsigned long long)mn,
+            (unsigned long long)mx, small);
   }
-  uint8_t *d_out = *d_out_io;
-  if (!d_out) {  // caller wants a library-owned buffer (scratch slot 1)
+  uint8_t *d_out = *a.d_out_io;
+  if (!d_out) {  // caller wants a library-owned buffer
     void *p;
-    ZT_TRY(scratch(c, 1, total ? total : 1, &p));
-    d_out = static_cast<uint8_t *>(p);
-    *d_out_io = d_out;
-  } else if (total > out_cap) {
-    *out_len = total;  // (the bytes needed)
+    ZT_TRY(scratch(c, kOut, plan.total ? plan.total : 1, &p));
+    *a.d_out_io = d_out = static_cast<uint8_t *>(p);
+  } else if (plan.total > a.out_cap) {  // (*out_len: the bytes needed)
     return set_error(ZT_E_ARG, "output capacity too small");
   }
-  // 4. expand (one wave per unit) and copy (one wave per segment)
-  void *d_chain, *d_desc;
-  const size_t chain_bytes = align256(chain.size() * sizeof(ChainUnit));
-  const size_t seg_bytes = align256(segs.size() * sizeof(SegJob));
-  const size_t ust_bytes = align256(chain.size() * 4);
-  ZT_TRY(scratch(c, 7, chain_bytes + seg_bytes + ust_bytes + align256(segs.size() * 4), &d_chain));
-  ZT_TRY(scratch(c, 3, (desc_total + 1024) * 2, &d_desc));  // + slack: chunked descriptor reads
-  ChainUnit *d_cu = static_cast<ChainUnit *>(d_chain);
-  SegJob *d_sj = reinterpret_cast<SegJob *>(static_cast<uint8_t *>(d_chain) + chain_bytes);
-  int32_t *d_ust = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(d_chain) + chain_bytes + seg_bytes);
-  int32_t *d_st = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(d_chain) + chain_bytes + seg_bytes + ust_bytes);
-  ChainUnit *h_cu = reinterpret_cast<ChainUnit *>(pin + meta_a);
-  SegJob *h_sj = reinterpret_cast<SegJob *>(pin + meta_a + align256(units_max * sizeof(ChainUnit)));
-  int32_t *h_ust = reinterpret_cast<int32_t *>(pin + meta_a + align256(units_max * sizeof(ChainUnit)) +
-                                               align256(units_max * sizeof(SegJob)));
-  int32_t *h_st = h_ust + align256(units_max * 4) / 4;
-  memcpy(h_cu, chain.data(), chain.size() * sizeof(ChainUnit));
-  memcpy(h_sj, segs.data(), segs.size() * sizeof(SegJob));
-  ZT_TRY(x_copy(d_cu, h_cu, chain.size() * sizeof(ChainUnit), s));
-  ZT_TRY(x_copy(d_sj, h_sj, segs.size() * sizeof(SegJob), s));
-  ResolveParams rp;
-  rp.tokens = static_cast<const uint32_t *>(d_tok);
-  rp.units = d_cu;
-  rp.segs = d_sj;
-  rp.out = d_out;
-  rp.desc = static_cast<uint16_t *>(d_desc);
-  rp.unit_status = d_ust;
-  rp.seg_status = d_st;
-  rp.nunits = (uint32_t)chain.size();
-  rp.nseg = (uint32_t)segs.size();
-  rp.marker = 0;
-  rp.in = d_in;
+  ChainRun run;
   IT("chain built");
-  ZT_TRY(resolve_segments_dev(rp, s));
+  ZT_TRY(resolve_chain_dev(c, plan.chain, plan.segs, plan.desc_total, d_tok, d_out, 0, a.d_in, pin.front, &run, s));
   ZT_TRY(timing_end(c, s, 2));
-  ZT_TRY(x_copy(h_ust, d_ust, chain.size() * 4, s));
-  ZT_TRY(x_copy(h_st, d_st, segs.size() * 4, s));
-  ZT_HIP(hipStreamSynchronize(s));
+  ZT_TRY(chain_statuses(run, s));
   IT("resolved");
-  ZT_TRY(timing_collect(c, &c->times.inflate_ms, &c->times.inflate_launches, 2));
-  ZT_TRY(timing_collect(c, &c->times.inflate_tok_ms, &c->times.inflate_toks, 3));
-  for (size_t i = 0; i < chain.size(); ++i)
-    if (h_ust[i] != ZT_OK) FALLBACK("unit %zu of %zu (chain): status %d\n", i, chain.size(), h_ust[i]);
-  for (size_t i = 0; i < segs.size(); ++i)
-    if (h_st[i] != ZT_OK) FALLBACK("segment %zu of %zu: status %d\n", i, segs.size(), h_st[i]);
-  c->times.inflate_paths[0]++;
+  return seg_done(a, run, "chain");
+}
+
+}  // namespace
+
+int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
+                         size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary) {
+  IT("start");
+  if (n < index + (1u << 14)) return 1;  // small: one wave is as fast
+  SegUnits U;
+  ZT_TRY(seg_find_units(c, d_in, n, index, s, &U));
+  uint32_t *d_tok;
+  SegPinned pin;
+  uint64_t *d_dbg;
+  ZT_TRY(seg_tokenize(c, d_in, n, U, s, &d_tok, &pin, &d_dbg));
+  const SegCall a{c, d_in, n, d_out_io, out_cap, out_len, end_ip, s, boundary};
+  bool resolved;
+  const int rc = seg_chain_device(a, U, d_tok, pin, /*plain=*/!d_dbg && !inf_debug(), &resolved);
+  if (rc || resolved) return rc;
+  return seg_chain_on_host(a, U, d_tok, pin, d_dbg);
+}
+
+// chain_kernel on host tables (zt_internal.h)
+extern "C" int zt_debug_chain(const TokResult *res, const uint8_t *restart, const uint64_t *tok_off, uint32_t units,
+                              uint64_t out_cap, uint64_t desc_cap, uint32_t max_seg, ChainInfo *info, ChainUnit *cu,
+                              SegJob *sj) {
+  if (!res || !restart || !tok_off || !info || !cu || !sj || units == 0 || units > CH_MAXU || max_seg == 0)
+    return set_error(ZT_E_ARG, "zt_debug_chain: bad argument");
+  DeviceCtx *c;
+  ZT_TRY(get_ctx(&c));
+  std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+  hipStream_t s = c->stream;
+  void *d_chain;
+  TokResult *d_res = nullptr;
+  uint8_t *d_restart = nullptr;
+  uint64_t *d_off = nullptr;
+  ZT_TRY(scratch_carved(c, kTokMeta, [&](void *base) {
+    Carve cv(base);
+    d_res = cv.take<TokResult>(units);
+    d_restart = cv.take<uint8_t>(units);
+    d_off = cv.take<uint64_t>(units);
+    return cv.bytes();
+  }));
+  ZT_TRY(scratch(c, kChain, chain_buf(nullptr, units, max_seg, 0, kChainTail).bytes, &d_chain));
+  const ChainBuf dev = chain_buf(d_chain, units, max_seg, 0, kChainTail);
+  ZT_HIP(hipMemcpyAsync(d_res, res, units * sizeof(TokResult), hipMemcpyHostToDevice, s));
+  ZT_HIP(hipMemsetAsync(d_restart, 0, 1, s));  // (the kernel reads restart[0] for a single unit too)
+  if (units > 1) ZT_HIP(hipMemcpyAsync(d_restart, restart, units - 1, hipMemcpyHostToDevice, s));
+  ZT_HIP(hipMemcpyAsync(d_off, tok_off, units * 8, hipMemcpyHostToDevice, s));
+  ChainInfo *d_info = reinterpret_cast<ChainInfo *>(dev.tail);
+  ZT_HIP(hipMemsetAsync(d_info, 0, sizeof(ChainInfo), s));
+  chain_kernel<<<1, CH_T, 0, s>>>(d_res, d_restart, d_off, units, out_cap, desc_cap, max_seg, dev.units, dev.segs,
+                                  d_info, nullptr, nullptr);
+  ZT_HIP(hipGetLastError());
+  ZT_HIP(hipMemcpyAsync(info, d_info, sizeof(ChainInfo), hipMemcpyDeviceToHost, s));
+  ZT_HIP(hipStreamSynchronize(s));
+  if (!info->ok) return ZT_OK;
+  if (info->nseg > max_seg) return set_error(ZT_E_INTERNAL, "zt_debug_chain: more segments than the bound");
+  ZT_HIP(hipMemcpyAsync(cu, dev.units, (size_t)units * sizeof(ChainUnit), hipMemcpyDeviceToHost, s));
+  ZT_HIP(hipMemcpyAsync(sj, dev.segs, (size_t)info->nseg * sizeof(SegJob), hipMemcpyDeviceToHost, s));
+  ZT_HIP(hipStreamSynchronize(s));
   return ZT_OK;
 }
 

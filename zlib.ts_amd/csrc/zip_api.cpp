@@ -28,10 +28,6 @@
 
 namespace zt {
 
-int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
-                              const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
-                              int *status);
-
 namespace {
 
 void put16(std::vector<uint8_t> &o, uint32_t v) {
@@ -336,7 +332,7 @@ int unzip_impl(const uint8_t *in, size_t n, int verify, const uint8_t *password,
   if (!defl.empty() || !encd.empty()) {
     ZT_TRY(get_ctx(&dc));
     ctx_lock = std::unique_lock<std::recursive_mutex>(dc->mu);
-    ZT_TRY(scratch(dc, 19, n + 64, &d_in));
+    ZT_TRY(scratch(dc, kContainerIn, n + 64, &d_in));
     ZT_TRY(upload(dc, d_in, in, n, dc->stream));
   }
   // protected entries: decrypted in place in the device copy, one lane each

@@ -118,6 +118,12 @@ int get_ctx(DeviceCtx **out) {
   return ZT_OK;
 }
 
+void host_stamp(const char *tag, const char *label) {
+  const double ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  fprintf(stderr, "[%s] %-28s %9.3f ms\n", tag, label, ms);
+}
+
 int scratch(DeviceCtx *c, int slot, size_t bytes, void **ptr) {
   if (bytes == 0) bytes = 16;
   if (c->buf_size[slot] < bytes) {
@@ -335,8 +341,9 @@ int pinned(DeviceCtx *c, size_t bytes, void **ptr, int slot) {
       c->pinned_size[slot] = 0;
     }
     size_t sz = bytes + bytes / 4;
-    // (slot 1, the inflate metadata, is written and read by q_copy kernels: coherent)
-    if (const hipError_t e = hipHostMalloc(&c->h_pinned[slot], sz, slot == 1 ? hipHostMallocCoherent : hipHostMallocDefault)) {
+    // (the inflate metadata is written and read by q_copy kernels: coherent)
+    if (const hipError_t e = hipHostMalloc(&c->h_pinned[slot], sz,
+                                           slot == kPinInflateMeta ? hipHostMallocCoherent : hipHostMallocDefault)) {
       c->h_pinned[slot] = nullptr;
       (void)hipGetLastError();
       return hip_fail(e, "hipHostMalloc (staging)");
@@ -348,7 +355,7 @@ int pinned(DeviceCtx *c, size_t bytes, void **ptr, int slot) {
 }
 
 int mailbox(DeviceCtx *c, size_t n, void **p) {
-  constexpr int kSlot = 8;
+  constexpr int kSlot = kPinMailbox;
   if (n < 4096) n = 4096;
   if (c->pinned_size[kSlot] < n) {
     if (c->h_pinned[kSlot]) {
@@ -414,7 +421,7 @@ static void host_copy(void *dst, const void *src, size_t n) {
 static int xfer_setup(DeviceCtx *c, uint8_t **buf) {
   for (int k = 0; k < 2; ++k) {
     void *p;
-    ZT_TRY(pinned(c, kXferChunk, &p, 2 + k));
+    ZT_TRY(pinned(c, kXferChunk, &p, kPinChunk0 + k));
     buf[k] = static_cast<uint8_t *>(p);
     if (!c->xfer_ev[k]) ZT_HIP(hipEventCreateWithFlags(&c->xfer_ev[k], hipEventDisableTiming));
   }
@@ -491,7 +498,7 @@ int pipeline_h2d_d2h(DeviceCtx *c, size_t np, const std::function<PipePiece(size
   uint8_t *stage[4];
   for (int k = 0; k < 4; ++k) {
     void *p;
-    ZT_TRY(pinned(c, kXferChunk, &p, 2 + k));
+    ZT_TRY(pinned(c, kXferChunk, &p, kPinChunk0 + k));
     stage[k] = static_cast<uint8_t *>(p);
     if (!c->xfer_ev[k]) ZT_HIP(hipEventCreateWithFlags(&c->xfer_ev[k], hipEventDisableTiming));
   }
@@ -800,7 +807,7 @@ int zt_dev_checksums(const void *d_in, size_t n, uint32_t crc_in, uint32_t adler
     return ZT_OK;
   }
   void *res;
-  ZT_TRY(scratch(c, 2, 16, &res));
+  ZT_TRY(scratch(c, kSmall, 16, &res));
   ZT_TRY(checksums_dev(c, (const uint8_t *)d_in, n, crc_out != nullptr, adler_out != nullptr, crc_in, adler_in,
                        (uint32_t *)res, s));
   uint32_t h[2];
@@ -823,7 +830,7 @@ static int checksums_host(const uint8_t *data, size_t len, uint32_t crc_in, uint
   }
   if (!data) return set_error(ZT_E_ARG, "null data");
   void *d;
-  ZT_TRY(scratch(c, 0, len, &d));
+  ZT_TRY(scratch(c, kIn, len, &d));
   ZT_TRY(upload(c, d, data, len, c->stream));
   return zt_dev_checksums(d, len, crc_in, adler_in, crc_out, adler_out, c->stream);
 }
@@ -874,7 +881,7 @@ int zt_release_scratch(void) {
     c->d_buf[k] = nullptr;
     c->buf_size[k] = 0;
   }
-  for (int k = 0; k < 10; ++k) {
+  for (int k = 0; k < kPinnedSlots; ++k) {
     if (c->h_pinned[k]) ZT_HIP(hipHostFree(c->h_pinned[k]));
     c->h_pinned[k] = nullptr;
     c->pinned_size[k] = 0;

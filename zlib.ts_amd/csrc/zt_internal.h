@@ -6,11 +6,13 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "../../include/zt.h"
 #include "dict_host.h"
+#include "inflate_chain.h"
 
 namespace zt {
 
@@ -47,6 +49,58 @@ struct CkAcc {
   CkPart part[kCkMaxWg];
 };
 
+// Device scratch slots (DeviceCtx::d_buf, scratch()).  Per slot: its owner, and
+// what a holder of its pointer may call while it still uses that pointer.
+enum ScratchSlot : int {
+  kIn = 0,          // the host entry points' input on the device; the holder may call any launcher (none asks for it)
+  kOut = 1,         // deflate output of the host entry points, and the library-owned inflate output:
+                    // inflate_segments_dev / general_dev / the batch decoders hand it out through *d_out_io
+                    // or as `d_out`; valid until the next inflate or deflate call on this context
+  kSmall = 2,       // a few job / result records of the entry points (and ZT_TOK_CHECK's words); no launcher call between
+  kDeflateOrDesc = 3,  // two users, never at once: the deflate pipeline's scratch (deflate_scratch, whole call)
+                    // and the two-phase inflate's descriptors (segment and batch paths: resolve only)
+  kTokens = 4,      // two-phase tokens (segment and batch paths): from tokenize to the end of resolve
+  kSyncCand = 5,    // inflate_segments_dev: sync candidates, steps 1-2 only
+  kTokMeta = 6,     // stops | restart flags | TokJob | TokResult (segment path), TokJob | TokResult (batch): whole call
+  kChain = 7,       // chain | segments | statuses (| ChainInfo) of the segment and batch paths: resolve only
+  kCkSeg = 8,       // checksums_dev's segment partials; inside the call
+  kCkBatch = 9,     // checksums_batch_dev's job tables; inside the call
+  kGenCand = 10,    // general inflate (inflate_gen.hip), 10-17: inside one general_dev call; it calls
+  kGenTokens = 11,  //   no launcher that asks for these or for another path's slots (it may take kOut)
+  kGenMeta = 12,
+  kGenBitmap = 13,
+  kGenChain = 14,
+  kGenDesc = 15,
+  kGenOut16 = 16,
+  kGenWindows = 17,
+  kSums = 18,       // per-item (crc, adler) of the batch calls; until they are copied back in the same call
+  kContainerIn = 19,  // unzip / gunzip member input (zip_api, container_api) and zt_gunzip_batch's member scan;
+                    // the holder may call the inflate and checksum launchers (none asks for it)
+  kSyncSort = 20,   // inflate_segments_dev: sort storage | keys | flags | positions | token offsets, up to the device chain
+  kStoredRuns = 21, // (unused)
+  kPipeOut = 22,    // pipelined host inflate's output; the holder calls inflate_parallel_dev (never asks for 22-25)
+  kPipeRing0 = 23,  // 23-25: its overflow ring, piece i's buffer reused once piece i - 3 has left the device
+  kGenJump = 26,    // general inflate's window pointer-jumping buffers
+  kFramed = 27,     // framed batch members (batch_api.cpp); inside the call
+  kTokOrder = 28,   // segment path: tokenize / expand launch order, up to resolve
+  kDict = 29,       // a preset dictionary (zt_dict.h: deflate history | inflate window | the whole dictionary);
+                    // the holder may call the batch deflate / inflate launchers
+  kScratchSlots
+};
+// Pinned host staging (DeviceCtx::h_pinned, pinned()).
+enum PinnedSlot : int {
+  kPinBatch = 0,        // batch data of the host entry points; inside the call
+  kPinInflateMeta = 1,  // inflate metadata (coherent): the segment path's tables and resolve_chain_dev's
+                        // chain / statuses; the segment path sizes it once for both, so its tables stay valid
+  kPinChunk0 = 2,       // 2-3 upload / download chunks (upload, download), 4-5 the three-stage pipeline's
+                        // download chunks (pipeline_h2d_d2h)
+  kPinGroupIn = 6,      // second input group of a grouped batch (batch_api.cpp)
+  kPinGroupOut = 7,     // its output group
+  kPinMailbox = 8,      // the readback mailbox (mailbox()): valid until the next mailbox / readback call
+  kPinUnused = 9,
+  kPinnedSlots
+};
+
 // One default stream per device plus grow-only scratch buffers, so the
 // host-pointer entry points do not hipMalloc on every call.
 struct DeviceCtx {
@@ -63,29 +117,52 @@ struct DeviceCtx {
   uint32_t *d_crc_shift = nullptr;  // checksum.hip merge constants (crc_shift_tables)
   CkAcc *d_ck_acc = nullptr;        // checksum merge accumulators (zeroed once, left zeroed by every call)
   // scratch
-  static constexpr int kSlots = 30;
-  void *d_buf[kSlots] = {};  // slot 8: checksum segment partials; 10-17: general inflate (inflate_gen.hip);
-                             // 20: segment inflate's sync-point sort (inflate_seg.hip); 21: stored runs;
-                             // 22: pipelined host inflate's output, 23-25: its overflow ring (inflate_api.cpp);
-                             // 26: general inflate's window pointer-jumping buffers; 27: framed batch members;
-                             // 28: segment inflate's tokenize launch order; 29: a preset dictionary
-                             // (zt_dict.h: deflate history | inflate window | the whole dictionary)
+  static constexpr int kSlots = kScratchSlots;
+  void *d_buf[kSlots] = {};  // (ScratchSlot)
   size_t buf_size[kSlots] = {};
   // second stream: checksums run beside the deflate pipeline in the containers
   hipStream_t aux = nullptr;
   hipEvent_t aux_ev = nullptr;
-  void *h_pinned[10] = {};  // pinned host staging: 0 batch data, 1 inflate metadata, 2-3 upload/download chunks,
-                            // 4-5 download chunks of the three-stage pipeline (pipeline_h2d_d2h),
-                            // 6-7 second input group / output group of a grouped batch (batch_api.cpp),
-                            // 8 the readback mailbox (mailbox())
-  hipEvent_t xfer_ev[4] = {};  // chunk buffer 2 + k's copy has finished
+  void *h_pinned[kPinnedSlots] = {};  // (PinnedSlot)
+  hipEvent_t xfer_ev[4] = {};  // chunk buffer kPinChunk0 + k's copy has finished
   hipStream_t up = nullptr, dn = nullptr;  // pipeline_h2d_d2h: H2D and D2H copy streams
   // zt_timing_enable: HIP-event kernel timing
   bool timing = false;
   hipEvent_t ev[8] = {};  // [2k, 2k+1]: interval k (0 match, 1 deflate pipeline, 2 inflate)
   zt_kernel_times times = {};
-  size_t pinned_size[10] = {};
+  size_t pinned_size[kPinnedSlots] = {};
 };
+
+// Carves one buffer into typed pieces, each 256-byte aligned, so that a
+// buffer's size and the pointers into it come from the same lines: with a
+// null base take() only counts (bytes() is then the size to allocate), with a
+// real base it hands out the pointers.  (align_up, the host code's one
+// rounding function, comes from inflate_chain.h.)
+class Carve {
+ public:
+  explicit Carve(void *base = nullptr) : base_(static_cast<uint8_t *>(base)) {}
+  template <typename T>
+  T *take(size_t count) {
+    T *p = base_ ? reinterpret_cast<T *>(base_ + at_) : nullptr;
+    at_ += align_up(count * sizeof(T), 256);
+    return p;
+  }
+  size_t bytes() const { return at_; }
+
+ private:
+  uint8_t *base_;
+  size_t at_ = 0;
+};
+
+// Host wall-clock stamps of a host driver's stages on stderr when the
+// environment variable `env` is set (measurement only): ZT_INF_TIMING in
+// inflate_seg.hip, ZT_BATCH_TIMING in inflate_api.cpp.
+void host_stamp(const char *tag, const char *label);  // zt_api.cpp: "[tag] label  <ms since the epoch>"
+#define ZT_STAMP(env, tag, label)                   \
+  do {                                              \
+    static const bool on_ = getenv(env) != nullptr; \
+    if (on_) ::zt::host_stamp(tag, label);          \
+  } while (0)
 
 // Records the begin / end event of interval k (0 or 1) when timing is on.
 int timing_begin(DeviceCtx *c, hipStream_t s, int k = 0);
@@ -95,15 +172,28 @@ int timing_collect(DeviceCtx *c, double *acc_ms, uint64_t *count, int k = 0);
 
 // Context of the calling thread's current device (created on first use).
 int get_ctx(DeviceCtx **out);
-// Grow-only device scratch slot `slot` to at least `bytes`.
+// Grow-only device scratch slot `slot` (a ScratchSlot) to at least `bytes`.
+// A slot that grows is freed and allocated again, so every earlier pointer
+// into it dies: hold no pointer into slot X across a call that may also ask
+// for slot X (the enum says, per slot, which calls a holder may make).  The
+// same holds for pinned().
 int scratch(DeviceCtx *c, int slot, size_t bytes, void **ptr);
-// Grow-only pinned host staging buffer `slot` (0 or 1) of at least `bytes`.
-int pinned(DeviceCtx *c, size_t bytes, void **ptr, int slot = 0);
+// Grow-only pinned host staging buffer `slot` (a PinnedSlot) of at least `bytes`.
+int pinned(DeviceCtx *c, size_t bytes, void **ptr, int slot = kPinBatch);
+// Scratch slot `slot` carved by carve(base) -> bytes (a Carve inside): called
+// with null for the size, then with the slot's base for the pointers.
+template <typename F>
+int scratch_carved(DeviceCtx *c, int slot, F &&carve) {
+  void *base;
+  ZT_TRY(scratch(c, slot, carve(nullptr), &base));
+  carve(base);
+  return ZT_OK;
+}
 // Small transfers between the host and the device (counts, per-unit
 // results, chain tables) go through pinned memory: a pageable destination
 // adds a staging copy inside the runtime.  q_copy(dst, src, n, s): a kernel
 // copy (either end device or pinned host memory).  mailbox(c, n): a pinned, coherent region of
-// >= n bytes (pinned slot 8), valid until the next mailbox call (one user at
+// >= n bytes (kPinMailbox), valid until the next mailbox call (one user at
 // a time: the context's caller thread).  readback(c, dst, src, n, s): n bytes
 // from the device to any host dst through the mailbox, synchronous.
 int q_copy(void *dst, const void *src, size_t n, hipStream_t s);
@@ -427,7 +517,11 @@ struct BatchExtras {
   // which is then no more than "failed" (not the reference's status)
   const uint8_t *speculative = nullptr;
 };
-struct DeviceCtx;
+// Decode `count` device-resident streams (stream i at d_in + in_off[i],
+// n[i] bytes, from index[i]); outputs are malloc'd.
+int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
+                              const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
+                              int *status);
 int inflate_batch_dev_streams_ex(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,
                                  const size_t *index, size_t count, uint8_t **out, size_t *out_len, size_t *end_ip,
                                  int *status, const uint8_t *d_hist, uint32_t hist_len, const BatchExtras *extras);
@@ -475,7 +569,7 @@ struct InfResult {
 
 // segment-parallel inflate (restart markers written by deflate); returns 1 when
 // the stream has no usable segments (caller decodes it with one wave)
-// (*d_out_io null: the output goes to scratch slot 1, returned in *d_out_io;
+// (*d_out_io null: the output goes to scratch slot kOut, returned in *d_out_io;
 // a caller-owned output too small for the stream: ZT_E_ARG with *out_len = the
 // bytes it needs).  boundary (a byte position, or ~0: none): the decode must
 // have a block boundary there -- a unit of the chain starts at it -- or the
@@ -483,25 +577,20 @@ struct InfResult {
 // real block boundary of the whole stream)
 int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
                          size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary = ~0ull);
-
+// The large-stream cascade (inflate_api.cpp): the segment path, then -- unless
+// allow_general is false or the segment path returned 2 (its chain ran out of
+// input: the general path cannot finish either) -- the general path.  A
+// library-owned output (*d_out_io null on entry) is reset between the two:
+// the segment path may have placed one before it gave up, and with that
+// pointer and no capacity the general path would refuse the stream.  A
+// caller-owned output is never reset.  Returns 0, 1 (decode with one wave), 2
+// or a negative status, as the two paths do.
+int inflate_parallel_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
+                         size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary = ~0ull,
+                         bool allow_general = true);
 
 // ---- two-phase token inflate (inflate_tok.hip) ----------------------------------
-// phase A: one unit = blocks from one sync point to the next
-struct TokJob {
-  uint64_t start;       // byte position (relative to `in`) of the unit's first block
-  uint64_t tok_off;     // first token slot
-  uint32_t tok_cap;     // token capacity
-  uint32_t stop_first;  // index of the first sync point after `start`
-  uint64_t end;         // end of the unit's input (batch: its stream's end), 0: TokParams::n
-};
-struct TokResult {
-  uint64_t out_len;   // bytes the unit's tokens produce
-  uint64_t end_bits;  // bit position after the unit's last block
-  uint32_t ntok;
-  int32_t status;
-  int32_t detail;
-  int32_t stop_idx;   // sync point where the unit stopped, -1 at BFINAL
-};
+// (TokJob, TokResult, ChainUnit, SegJob, ChainInfo: inflate_chain.h)
 struct TokParams {
   const uint8_t *in;
   uint64_t n;
@@ -522,28 +611,6 @@ struct TokParams {
   // input; 0: the tokenizer writes a literal token per stored byte
   int run_tokens;
 };
-constexpr uint32_t kStoredRunMin = 1024;
-// phase B: units of the chain, grouped by segment
-struct ChainUnit {
-  uint64_t tok_off;
-  uint64_t out_off;  // absolute output offset
-  uint64_t seg_off;  // output offset of the unit's segment
-  uint64_t desc_off; // its descriptors (segments start 128-aligned)
-  uint32_t ntok;
-  uint32_t out_len;
-};
-struct SegJob {
-  uint32_t first, count;  // chain units [first, first + count)
-};
-// the chain built on the device (inflate_seg.hip chain_kernel); ok == 0: not
-// the common case, expand / copy return at once and the host walks the chain
-struct ChainInfo {
-  int32_t ok;
-  uint32_t nseg;
-  uint64_t total;       // output bytes
-  uint64_t end_bits;    // bit after the last unit's last block
-  uint64_t desc_total;  // descriptors
-};
 struct ResolveParams {
   const uint32_t *tokens;
   const ChainUnit *units;
@@ -559,9 +626,73 @@ struct ResolveParams {
   const ChainInfo *info = nullptr;  // device-built chain: nothing to do unless info->ok; nseg = info->nseg
   const uint32_t *order = nullptr;  // expand: workgroup g takes unit order[g] (null: unit g)
 };
+// TokParams::simt of every caller: ZT_TOK_SIMT=0 selects the one-lane body decode (A/B)
+inline int tok_simt_env() {
+  static const char *e = getenv("ZT_TOK_SIMT");
+  return e ? atoi(e) != 0 : 1;
+}
 int tokenize_units_dev(const TokParams &p, hipStream_t s);
 int resolve_segments_dev(const ResolveParams &p, hipStream_t s);
 int expand_units_dev(const ResolveParams &p, hipStream_t s);
+
+// A chain buffer, in a device scratch slot or its mirror in pinned staging:
+// [chain units | segment jobs | extra | unit statuses | segment statuses | tail]
+// (extra: the general path's GenSeg table; tail: the device chain's ChainInfo
+// and boundary flag, read back with the statuses in one copy).
+struct ChainBuf {
+  ChainUnit *units;
+  SegJob *segs;
+  uint8_t *extra;
+  int32_t *unit_status;
+  int32_t *seg_status;
+  uint8_t *tail;
+  size_t bytes;  // all of it
+};
+inline ChainBuf chain_buf(void *base, size_t units, size_t segs, size_t extra_bytes = 0, size_t tail_bytes = 0) {
+  Carve cv(base);
+  ChainBuf b;
+  b.units = cv.take<ChainUnit>(units);
+  b.segs = cv.take<SegJob>(segs);
+  b.extra = cv.take<uint8_t>(extra_bytes);
+  b.unit_status = cv.take<int32_t>(units);
+  b.seg_status = cv.take<int32_t>(segs);
+  b.tail = cv.take<uint8_t>(tail_bytes);
+  b.bytes = cv.bytes();
+  return b;
+}
+// A host-built chain on its way through the resolve kernels (inflate_resolve.cpp).
+struct ChainRun {
+  // dev: in a scratch slot.  host: its mirror in kPinInflateMeta, set by
+  // resolve_chain_dev alone (chain_statuses needs it); general_dev, which
+  // keeps its own transfers, leaves it empty
+  ChainBuf dev, host;
+  uint32_t nunits, nseg;
+};
+ResolveParams resolve_params(const ChainRun &run, const uint32_t *tokens, uint16_t *desc, uint8_t *out,
+                             int32_t marker, const uint8_t *in);
+// resolve_chain_dev: carves kChain and the mirror, copies chain and segments
+// to the device (x_copy from the mirror), takes descriptors for desc_total
+// output bytes in kDeflateOrDesc, then expand and copy (resolve_segments_dev).
+// pin_front: bytes at the front of kPinInflateMeta that the caller still
+// reads (it has sized the slot for both, so the slot does not move).
+int resolve_chain_dev(DeviceCtx *c, const std::vector<ChainUnit> &chain, const std::vector<SegJob> &segs,
+                      uint64_t desc_total, const uint32_t *tokens, uint8_t *out, int32_t marker, const uint8_t *in,
+                      size_t pin_front, ChainRun *run, hipStream_t s);
+// chain_statuses: both status arrays into the mirror (run.host.unit_status /
+// seg_status), then waits for the stream.
+int chain_statuses(const ChainRun &run, hipStream_t s);
+// debug (inflate_seg.hip; exported, not part of include/zt.h): chain_kernel on
+// host tables of `units` units (restart: units - 1 flags) with the given
+// capacities; info, and when info->ok the `units` chain units and info->nseg
+// segment jobs, come back (cu: room for units, sj: for max_seg)
+extern "C" int zt_debug_chain(const TokResult *res, const uint8_t *restart, const uint64_t *tok_off, uint32_t units,
+                              uint64_t out_cap, uint64_t desc_cap, uint32_t max_seg, ChainInfo *info, ChainUnit *cu,
+                              SegJob *sj);
+// debug: seg_chain_host on the same tables, in the same shape (cu and sj: room
+// for `units`; *nchain: units on the chain; *outcome: ChainPlan::Outcome)
+extern "C" int zt_debug_chain_host(const TokResult *res, const uint8_t *restart, const uint64_t *tok_off,
+                                   uint32_t units, ChainInfo *info, ChainUnit *cu, SegJob *sj, uint32_t *nchain,
+                                   int *outcome);
 
 // ---- general speculative inflate (inflate_gen.hip) ---------------------------------
 // A stream without sync points is cut at fixed bit positions; each *unit* is

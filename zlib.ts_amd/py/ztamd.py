@@ -144,6 +144,8 @@ def _load():
         # debug (csrc/zt_internal.h)
         "zt_debug_match_modes": ([P(ctypes.c_uint64)], ctypes.c_int),
         "zt_debug_head_formats": ([P(ctypes.c_uint64)], ctypes.c_int),
+        "zt_debug_chain": ([vp, vp, vp, u32, ctypes.c_uint64, ctypes.c_uint64, u32, vp, vp, vp], ctypes.c_int),
+        "zt_debug_chain_host": ([vp, vp, vp, u32, vp, vp, vp, P(u32), P(ctypes.c_int)], ctypes.c_int),
         # include/zt_zipcrypto.h
         "zt_zipcrypto_encrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
         "zt_zipcrypto_decrypt_batch": ([P(vp), P(sz), sz, P(vp), P(sz), u8pp], ctypes.c_int),
@@ -870,6 +872,45 @@ def debug_head_formats():
     v = (ctypes.c_uint64 * 2)()
     _check(lib.zt_debug_head_formats(v))
     return int(v[0]), int(v[1])
+
+
+def debug_chain(res, restart, tok_off, out_cap, desc_cap, max_seg, host=False):
+    """The segment chain of one stream's unit tables (csrc/inflate_chain.h), built by
+    chain_kernel on the device or, host=True, by seg_chain_host.  res: numpy
+    records (out_len u8, end_bits u8, ntok u4, status i4, detail i4, stop_idx
+    i4), restart: u1[units - 1], tok_off: u8[units].  Returns (info, units,
+    segs): info = dict(ok, nseg, total, end_bits, desc_total), units / segs numpy
+    records of ChainUnit / SegJob (empty unless info['ok']); host=True adds
+    info['outcome'] (0 built, 1 fallback, 2 ran out of input)."""
+    import numpy as np
+
+    cu_t = np.dtype([("tok_off", "<u8"), ("out_off", "<u8"), ("seg_off", "<u8"), ("desc_off", "<u8"),
+                     ("ntok", "<u4"), ("out_len", "<u4")])
+    sj_t = np.dtype([("first", "<u4"), ("count", "<u4")])
+    info_t = np.dtype([("ok", "<i4"), ("nseg", "<u4"), ("total", "<u8"), ("end_bits", "<u8"), ("desc_total", "<u8")])
+    n = len(res)
+    res = np.ascontiguousarray(res)
+    assert res.dtype.itemsize == 32 and len(tok_off) == n
+    rs = np.zeros(max(n, 1), dtype=np.uint8)
+    rs[:n - 1] = restart
+    to = np.ascontiguousarray(tok_off, dtype=np.uint64)
+    info = np.zeros(1, dtype=info_t)
+    cu = np.zeros(n, dtype=cu_t)
+    sj = np.zeros(max(n if host else max_seg, 1), dtype=sj_t)
+    if host:
+        nchain, outcome = ctypes.c_uint32(0), ctypes.c_int(0)
+        _check(lib.zt_debug_chain_host(res.ctypes.data, rs.ctypes.data, to.ctypes.data, n, info.ctypes.data,
+                                       cu.ctypes.data, sj.ctypes.data, ctypes.byref(nchain), ctypes.byref(outcome)))
+        cu = cu[:nchain.value]
+    else:
+        _check(lib.zt_debug_chain(res.ctypes.data, rs.ctypes.data, to.ctypes.data, n, out_cap, desc_cap, max_seg,
+                                  info.ctypes.data, cu.ctypes.data, sj.ctypes.data))
+    d = {k: int(info[0][k]) for k in info_t.names}
+    if host:
+        d["outcome"] = outcome.value
+    if not d["ok"]:
+        return d, cu[:0], sj[:0]
+    return d, cu, sj[:d["nseg"]]
 
 
 def scratch_bytes():
