@@ -3,7 +3,9 @@
 zlib.ts_amd/csrc/gunzip_chain.h over hand-made candidate and decode tables)
 built with ASan + UBSan as a stand-alone program and run on the CPU, the same
 for tools/inflate_chain_check.cpp (the segment and batch chains of
-zlib.ts_amd/csrc/inflate_chain.h), and the ABI of include/zt_container_batch.h."""
+zlib.ts_amd/csrc/inflate_chain.h) and for tools/batch_plan_check.cpp (the host
+batch layer's arithmetic and fan-out, zlib.ts_amd/csrc/batch_plan.h), and the
+ABI of include/zt_container_batch.h."""
 import ctypes
 import os
 import re
@@ -39,6 +41,23 @@ def test_inflate_chain_check_sanitized(tmp_path):
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     assert p.stdout.strip().endswith("inflate_chain_check ok")
+
+
+@pytest.mark.skipif(not shutil.which("g++"), reason="g++ missing")
+def test_batch_plan_check_sanitized(tmp_path):
+    """tools/batch_plan_check.cpp: the host batch layer's arithmetic
+    (zlib.ts_amd/csrc/batch_plan.h: device splits, staging layout, upload
+    chunks, pipeline groups, output bounds, the option resolver) against slow
+    re-statements, and the fan-out's collection of each share's code and
+    message for 1 and 3 stub shares"""
+    exe = str(tmp_path / "batch_plan_check")
+    b = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-o", exe, os.path.join(ROOT, "tools", "batch_plan_check.cpp")],
+                       capture_output=True, text=True, timeout=300)
+    assert b.returncode == 0, b.stderr[-3000:]
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    assert p.stdout.strip().endswith("batch_plan_check ok")
 
 
 def test_header_declares_what_the_binding_binds():

@@ -134,7 +134,7 @@ def test_pipelined_inflate_zlib_stream(zt):
     assert ip == len(s) and back == data
 
 
-# ---- the host output pool (zt_api.cpp host_out): zt_free hands large outputs
+# ---- the host output pool (host_mem.cpp host_out): zt_free hands large outputs
 # back, the next output of a similar size reuses the buffer registered with
 # HIP, and copies to / from it go by DMA without staging.  The bench's host
 # round trip exactly: deflate output pointer straight into zt_inflate_raw.

@@ -15,14 +15,10 @@
 // new Deflate(input).compress() (src/Deflate.ts:60-99) and
 // new RawDeflate(input).compress() (src/RawDeflate.ts:87-114).
 #include <algorithm>
-#include <chrono>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "zt_internal.h"
@@ -37,9 +33,6 @@ constexpr uint64_t kBlk = 32768;
 // on stderr per share) -- packing into pinned staging and framing the members
 // are the host work that has to keep up with k devices on a node
 // (tools/c4_host_stages.py).  Measurement only.
-double stage_now() {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 bool stages_on() {
   static const bool on = getenv("ZT_BATCH_STAGES") != nullptr;
   return on;
@@ -57,8 +50,6 @@ struct StageTimes {
             wall_ms);
   }
 };
-
-size_t round_blk(size_t n) { return (n + kBlk - 1) / kBlk * kBlk; }
 
 // fills out[i] (malloc'd: prefix | stream | trailer) for item i
 struct Framing {
@@ -94,7 +85,7 @@ uint8_t *frame_slab(const Framing &fr, const uint64_t *oo, size_t nb, std::vecto
   size_t tot = 0;
   for (size_t j = 0; j < nb; ++j) {
     soff[j] = tot;
-    tot += (fr.prefix.size() + (oo[j + 1] - oo[j]) + fr.trailer + 64) & ~size_t(63);
+    tot += slab_stride(fr.prefix.size(), oo[j + 1] - oo[j], fr.trailer);
   }
   return slab_out(tot, nb);
 }
@@ -109,34 +100,32 @@ uint8_t *frame_slab(const Framing &fr, const uint64_t *oo, size_t nb, std::vecto
 // spans two), so every member is the one the single pipeline writes.
 constexpr uint64_t kGroupMin = 256ull << 20;
 
-int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size_t> &work,
-                  const std::vector<uint64_t> &off, const std::vector<uint64_t> &len, uint64_t padded, int ct, int lv,
-                  const Framing &fr, uint8_t **out, size_t *out_len, StageTimes &tm, const DictHist *dh) {
+int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &work,
+                  const PackLayout &L, const std::vector<uint64_t> &len, int ct, int lv, const Framing &fr,
+                  uint8_t **out, size_t *out_len, StageTimes &tm, const DictHist *dh) {
   const size_t m = work.size();
+  const std::vector<size_t> &off = L.off;
+  const uint64_t padded = L.total;
   const bool sums = fr.kind != Framing::RAW;
   // groups [gk[g], gk[g + 1]) of items
   // tuning hook: ZT_BATCH_GROUPS = groups per share (default 6)
   static const int ng_env = getenv("ZT_BATCH_GROUPS") ? atoi(getenv("ZT_BATCH_GROUPS")) : 0;
   const uint64_t target = std::max<uint64_t>(padded / (ng_env > 0 ? ng_env : 6), 64ull << 20);
-  std::vector<size_t> gk{0};
-  for (size_t k = 0; k < m; ++k)
-    if (k + 1 < m && off[k + 1] - off[gk.back()] >= target) gk.push_back(k + 1);
-  gk.push_back(m);
+  const std::vector<size_t> gk = group_cuts(off, m, padded, target);
   const size_t ng = gk.size() - 1;
   auto gbeg = [&](size_t g) { return off[gk[g]]; };
   auto gend = [&](size_t g) { return gk[g + 1] < m ? off[gk[g + 1]] : padded; };
-  auto obound = [](uint64_t p) { return (p + p / 8 + 1024 * (p / kBlk + 1) + 4096 + 255) & ~uint64_t(255); };
-  uint64_t gmax = 0, obmax = 0, obsum = 0;
+  uint64_t gmax = 0, obmax = 0;
   std::vector<uint64_t> ooff(ng + 1, 0);  // device output region of group g
   for (size_t g = 0; g < ng; ++g) {
+    const uint64_t ob = batch_out_bound(gend(g) - gbeg(g), 256);
     gmax = std::max(gmax, gend(g) - gbeg(g));
-    obmax = std::max(obmax, obound(gend(g) - gbeg(g)));
-    ooff[g + 1] = ooff[g] + obound(gend(g) - gbeg(g));
+    obmax = std::max(obmax, ob);
+    ooff[g + 1] = ooff[g] + ob;
   }
-  obsum = ooff[ng];
   void *d_in, *d_out, *d_scr, *d_sums = nullptr, *p;
   ZT_TRY(scratch(c, kIn, padded + 64, &d_in));
-  ZT_TRY(scratch(c, kOut, obsum, &d_out));
+  ZT_TRY(scratch(c, kOut, ooff[ng], &d_out));
   const size_t ss = deflate_batch_scratch_bytes(c, gmax);
   ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
   if (sums) ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
@@ -147,146 +136,73 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const std::vector<size
   stage_in[1] = static_cast<uint8_t *>(p);
   ZT_TRY(pinned(c, obmax, &p, kPinGroupOut));
   stage_out = static_cast<uint8_t *>(p);
-  if (!c->up) ZT_HIP(hipStreamCreateWithFlags(&c->up, hipStreamNonBlocking));
-  if (!c->dn) ZT_HIP(hipStreamCreateWithFlags(&c->dn, hipStreamNonBlocking));
-  std::vector<hipEvent_t> landed(ng, nullptr), staged(2, nullptr);
-  struct EvFree {
-    std::vector<hipEvent_t> &a, &b;
-    ~EvFree() {
-      for (auto e : a)
-        if (e) (void)hipEventDestroy(e);
-      for (auto e : b)
+  struct Staged {  // stage_in[k]'s last upload has left it
+    hipEvent_t ev[2] = {};
+    ~Staged() {
+      for (auto e : ev)
         if (e) (void)hipEventDestroy(e);
     }
-  } ev_free{landed, staged};
-  for (auto &e : landed) ZT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto &e : staged) ZT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  } staged;
+  for (auto &e : staged.ev) ZT_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 
   std::vector<uint32_t> hsums(2 * m, 0);
   std::vector<uint64_t> oo(m + ng, 0);  // group g's stream offsets at oo[gk[g] + g ..]
-  std::mutex mu;
-  std::condition_variable cv;
-  size_t uploaded = 0, computed = 0;
-  int err = 0;
-  std::string err_msg;
-  auto fail = [&](int rc) {
-    std::lock_guard<std::mutex> lk(mu);
-    if (!err) {
-      err = rc;
-      err_msg = zt_last_error_message();
-    }
-    cv.notify_all();
-  };
-  auto wait_for = [&](const size_t &counter, size_t g) {
-    std::unique_lock<std::mutex> lk(mu);
-    cv.wait(lk, [&] { return counter > g || err; });
-    return err == 0;
-  };
-  const int dev = c->phys;
-  auto up_stage = [&]() -> int {
-    ZT_HIP(hipSetDevice(dev));
-    for (size_t g = 0; g < ng; ++g) {
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        if (err) return ZT_OK;
-      }
-      uint8_t *st = stage_in[g & 1];
-      if (g >= 2) ZT_HIP(hipEventSynchronize(staged[g & 1]));  // its previous upload has left
-      const uint64_t b = gbeg(g), nb = gk[g + 1] - gk[g];
-      const double t0 = stage_now();
-      parallel_copy(nb, [&](size_t j) {
-        const size_t k = gk[g] + j;
-        copy_to_staging(st + off[k] - b, in[work[k]], len[k]);
-        memset(st + off[k] - b + len[k], 0, round_blk(len[k]) - len[k]);
-      }, gend(g) - b);
-      tm.pack_ms += stage_now() - t0;  // (this thread only)
-      ZT_HIP(hipMemcpyAsync((uint8_t *)d_in + b, st, gend(g) - b, hipMemcpyHostToDevice, c->up));
-      ZT_HIP(hipEventRecord(staged[g & 1], c->up));
-      ZT_HIP(hipEventRecord(landed[g], c->up));
-      std::lock_guard<std::mutex> lk(mu);
-      uploaded = g + 1;
-      cv.notify_all();
-    }
-    ZT_HIP(hipStreamSynchronize(c->up));
+  StagePipe pipe(c, ng);
+  auto up_stage = [&](size_t g) -> int {
+    uint8_t *st = stage_in[g & 1];
+    if (g >= 2) ZT_HIP(hipEventSynchronize(staged.ev[g & 1]));  // its previous upload has left
+    const double t0 = now_ms();
+    pack_items(st, in, n, work, L, gk[g], gk[g + 1], true, gend(g) - gbeg(g));
+    tm.pack_ms += now_ms() - t0;  // (this thread only)
+    ZT_HIP(hipMemcpyAsync((uint8_t *)d_in + gbeg(g), st, gend(g) - gbeg(g), hipMemcpyHostToDevice, c->up));
+    ZT_HIP(hipEventRecord(staged.ev[g & 1], c->up));
     return ZT_OK;
   };
-  auto dn_stage = [&]() -> int {
-    ZT_HIP(hipSetDevice(dev));
-    for (size_t g = 0; g < ng; ++g) {
-      if (!wait_for(computed, g)) return ZT_OK;
-      const size_t k0 = gk[g], nb = gk[g + 1] - k0;
-      const uint64_t *go = &oo[k0 + g];
-      ZT_HIP(hipMemcpyAsync(stage_out, (uint8_t *)d_out + ooff[g], go[nb], hipMemcpyDeviceToHost, c->dn));
-      ZT_HIP(hipStreamSynchronize(c->dn));
-      std::vector<int> rcs(nb, ZT_OK);
-      std::vector<size_t> soff;
-      const double t0 = stage_now();
-      uint8_t *slab = frame_slab(fr, go, nb, soff);
-      if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
-      parallel_copy(nb, [&](size_t j) {
-        const size_t k = k0 + j, i = work[k];
-        rcs[j] = frame_item(fr, len[k], stage_out + go[j], go[j + 1] - go[j], hsums[2 * k], hsums[2 * k + 1], &out[i],
-                            &out_len[i], slab + soff[j]);
-      }, go[nb]);
-      tm.frame_ms += stage_now() - t0;  // (this thread only)
-      tm.out_bytes += go[nb];
-      for (int rc : rcs)
-        if (rc) return rc;
-    }
-    return ZT_OK;
-  };
-  std::thread tu([&] {
-    if (int rc = up_stage()) fail(rc);
-  });
-  std::thread td([&] {
-    if (int rc = dn_stage()) fail(rc);
-  });
-  for (size_t g = 0; g < ng; ++g) {
-    if (!wait_for(uploaded, g)) break;
+  auto compute = [&](size_t g) -> int {
     const size_t k0 = gk[g], nb = gk[g + 1] - k0;
     const uint64_t b = gbeg(g);
     std::vector<uint64_t> ro(nb), rl(len.begin() + k0, len.begin() + k0 + nb);
     for (size_t j = 0; j < nb; ++j) ro[j] = off[k0 + j] - b;
-    auto step = [&]() -> int {
-      ZT_HIP(hipStreamWaitEvent(c->stream, landed[g], 0));
-      if (sums) {
-        ZT_HIP(hipStreamWaitEvent(c->aux, landed[g], 0));
-        ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(),
-                                   (uint32_t *)d_sums + 2 * k0, c->aux));
-        ZT_HIP(hipMemcpyAsync(hsums.data() + 2 * k0, (uint32_t *)d_sums + 2 * k0, 8 * nb, hipMemcpyDeviceToHost,
-                              c->aux));
-      }
-      ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), ct, lv,
-                                   (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, c->stream, dh));
-      if (sums) ZT_HIP(hipStreamSynchronize(c->aux));
-      return ZT_OK;
-    };
-    if (int rc = step()) {
-      fail(rc);
-      break;
+    if (sums) {
+      ZT_HIP(hipStreamWaitEvent(c->aux, pipe.landed(g), 0));
+      ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), (uint32_t *)d_sums + 2 * k0,
+                                 c->aux));
+      ZT_HIP(hipMemcpyAsync(hsums.data() + 2 * k0, (uint32_t *)d_sums + 2 * k0, 8 * nb, hipMemcpyDeviceToHost,
+                            c->aux));
     }
-    std::lock_guard<std::mutex> lk(mu);
-    computed = g + 1;
-    cv.notify_all();
-  }
-  tu.join();
-  td.join();
+    ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), ct, lv,
+                                 (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, c->stream, dh));
+    if (sums) ZT_HIP(hipStreamSynchronize(c->aux));
+    return ZT_OK;
+  };
+  auto dn_stage = [&](size_t g) -> int {
+    const size_t k0 = gk[g], nb = gk[g + 1] - k0;
+    const uint64_t *go = &oo[k0 + g];
+    ZT_HIP(hipMemcpyAsync(stage_out, (uint8_t *)d_out + ooff[g], go[nb], hipMemcpyDeviceToHost, c->dn));
+    ZT_HIP(hipStreamSynchronize(c->dn));
+    std::vector<int> rcs(nb, ZT_OK);
+    std::vector<size_t> soff;
+    const double t0 = now_ms();
+    uint8_t *slab = frame_slab(fr, go, nb, soff);
+    if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
+    parallel_copy(nb, [&](size_t j) {
+      const size_t k = k0 + j, i = work[k];
+      rcs[j] = frame_item(fr, len[k], stage_out + go[j], go[j + 1] - go[j], hsums[2 * k], hsums[2 * k + 1], &out[i],
+                          &out_len[i], slab + soff[j]);
+    }, go[nb]);
+    tm.frame_ms += now_ms() - t0;  // (this thread only)
+    tm.out_bytes += go[nb];
+    for (int rc : rcs)
+      if (rc) return rc;
+    return ZT_OK;
+  };
   tm.groups = ng;
-  if (err) return set_error(err, err_msg);
-  return ZT_OK;
+  return pipe.run(up_stage, compute, dn_stage);
 }
 
-// one device's share: items `ids` of the batch
-int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids, int ct,
-                    int lv, const Framing &fr, uint8_t **out, size_t *out_len, std::string *err, const HostDict &hd) {
-  auto fail = [&](int rc) {
-    *err = zt_last_error_message();
-    return rc;
-  };
-  if (zt_set_device(dev)) return fail(ZT_E_NO_DEVICE);
-  DeviceCtx *c;
-  if (int rc = get_ctx(&c)) return fail(rc);
-  std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+// one device's share: items `ids` of the batch (for_each_device: c is locked)
+int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids, int ct,
+                    int lv, const Framing &fr, uint8_t **out, size_t *out_len, const HostDict &hd) {
   const bool sums = fr.kind != Framing::RAW;
   // empty inputs: a final empty stored block, as the one-buffer calls write
   // (deflate.hip) -- no device work
@@ -294,8 +210,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
   for (size_t i : ids) {
     if (n[i] == 0) {
       static const uint8_t empty_stored[5] = {0x01, 0x00, 0x00, 0xFF, 0xFF};
-      const int rc = frame_item(fr, 0, empty_stored, 5, 0, 1, &out[i], &out_len[i]);
-      if (rc) return fail(rc);
+      ZT_TRY(frame_item(fr, 0, empty_stored, 5, 0, 1, &out[i], &out_len[i]));
     } else {
       work.push_back(i);
     }
@@ -307,67 +222,50 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
   const DictHist *dh = nullptr;
   std::vector<uint8_t> dict_img;
   if (hd.dict_len && ct != 0) {
-    const DictLayout L = dict_layout(hd.dict_len);
+    const DictLayout D = dict_layout(hd.dict_len);
     void *d_dict;
-    if (int rc = scratch(c, kDict, L.hist, &d_dict)) return fail(rc);
-    dict_img.resize(L.hist);
-    dict_fill_history(L, hd.dict, dict_img.data());
-    ZT_HIP(hipMemcpyAsync(d_dict, dict_img.data(), L.hist, hipMemcpyHostToDevice, c->stream));
+    ZT_TRY(scratch(c, kDict, D.hist, &d_dict));
+    dict_img.resize(D.hist);
+    dict_fill_history(D, hd.dict, dict_img.data());
+    ZT_HIP(hipMemcpyAsync(d_dict, dict_img.data(), D.hist, hipMemcpyHostToDevice, c->stream));
     ZT_HIP(hipStreamSynchronize(c->stream));
-    dict_dev = DictHist{static_cast<const uint8_t *>(d_dict), L.hist, L.floor};
+    dict_dev = DictHist{static_cast<const uint8_t *>(d_dict), D.hist, D.floor};
     dh = &dict_dev;
   }
   const size_t m = work.size();
-  std::vector<uint64_t> off(m), len(m);
-  uint64_t padded = 0, in_bytes = 0;
-  for (size_t k = 0; k < m; ++k) {
-    off[k] = padded;
-    len[k] = n[work[k]];
-    padded += round_blk(len[k]);
-    in_bytes += len[k];
-  }
+  const PackLayout L = pack_layout(n, work, kBlk, 1);  // every item from a 32 KiB boundary
+  const std::vector<size_t> &off = L.off;
+  const uint64_t padded = L.total;
+  std::vector<uint64_t> len(m);
+  uint64_t in_bytes = 0;
+  for (size_t k = 0; k < m; ++k) in_bytes += len[k] = n[work[k]];
   StageTimes tm;
   tm.items = m;
   tm.in_bytes = in_bytes;
-  const double t_start = stage_now();
+  const double t_start = now_ms();
   struct Report {
     StageTimes &tm;
     double t0;
     int dev;
     ~Report() {
-      tm.wall_ms = stage_now() - t0;
+      tm.wall_ms = now_ms() - t0;
       tm.report(dev);
     }
-  } report{tm, t_start, dev};
-  if (ct != 0 && padded >= kGroupMin && m >= 2) {
-    const int rc = batch_grouped(c, in, work, off, len, padded, ct, lv, fr, out, out_len, tm, dh);
-    return rc ? fail(rc) : ZT_OK;
-  }
-  void *d_in, *h_stage;
-  if (int rc = scratch(c, kIn, padded + 64, &d_in)) return fail(rc);
-  if (int rc = pinned(c, padded, &h_stage, kPinBatch)) return fail(rc);
-  uint8_t *stage = static_cast<uint8_t *>(h_stage);
-  const double t_pack = stage_now();
-  parallel_copy(m, [&](size_t k) {
-    copy_to_staging(stage + off[k], in[work[k]], len[k]);
-    memset(stage + off[k] + len[k], 0, round_blk(len[k]) - len[k]);
-  }, in_bytes);
-  tm.pack_ms += stage_now() - t_pack;
+  } report{tm, t_start, c->device};
+  if (ct != 0 && padded >= kGroupMin && m >= 2)
+    return batch_grouped(c, in, n, work, L, len, ct, lv, fr, out, out_len, tm, dh);
+  void *d_in;
+  ZT_TRY(pack_upload(c, in, n, work, L, PackMode{true, false, in_bytes, &tm.pack_ms}, &d_in));
   tm.groups = 1;
-  ZT_HIP(hipMemcpyAsync(d_in, stage, padded, hipMemcpyHostToDevice, c->stream));
   // checksums on the second stream, over the same device bytes
   std::vector<uint32_t> hsums(2 * m, 0);
   void *d_sums = nullptr;
-  struct AuxWait {
-    hipStream_t s;
-    ~AuxWait() { (void)hipStreamSynchronize(s); }
-  } aux_wait{c->aux};
+  AuxWait aux_wait{c->aux};
   if (sums) {
-    if (int rc = scratch(c, kSums, 8 * m, &d_sums)) return fail(rc);
+    ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
     ZT_HIP(hipEventRecord(c->aux_ev, c->stream));
     ZT_HIP(hipStreamWaitEvent(c->aux, c->aux_ev, 0));
-    if (int rc = checksums_batch_dev(c, (const uint8_t *)d_in, m, off.data(), len.data(), (uint32_t *)d_sums, c->aux))
-      return fail(rc);
+    ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in, m, off.data(), len.data(), (uint32_t *)d_sums, c->aux));
     ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * m, hipMemcpyDeviceToHost, c->aux));
   }
   std::vector<uint64_t> oo(m + 1, 0);
@@ -378,7 +276,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     uint64_t tot = 0;
     for (size_t k = 0; k < m; ++k) {
       oo[k] = tot;
-      tot += len[k] + 5 * ((len[k] + 65534) / 65535);
+      tot += stored_len(len[k]);
     }
     oo[m] = tot;
     stored_host.resize(tot);
@@ -398,14 +296,12 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     }
     body_host = stored_host.data();
   } else {
-    const size_t ob = padded + padded / 8 + 1024 * (padded / kBlk + 1) + 4096;
     void *d_out, *d_scr;
-    if (int rc = scratch(c, kOut, ob, &d_out)) return fail(rc);
+    ZT_TRY(scratch(c, kOut, batch_out_bound(padded), &d_out));
     const size_t ss = deflate_batch_scratch_bytes(c, padded);
-    if (int rc = scratch(c, kDeflateOrDesc, ss, &d_scr)) return fail(rc);
-    if (int rc = deflate_batch_dev_run(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv,
-                                       (uint8_t *)d_out, oo.data(), d_scr, ss, c->stream, dh))
-      return fail(rc);
+    ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
+    ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv, (uint8_t *)d_out,
+                                 oo.data(), d_scr, ss, c->stream, dh));
     // The members are framed on the device (prefix | stream | trailer, at
     // their slab offsets) and come back with one copy -- straight into the
     // slab when it is a registered pool buffer (a caller batching again after
@@ -413,7 +309,7 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     // framing (the slab filled from a staged copy of the streams) was a
     // quarter of a device thread's host time on a node's worth of devices
     // (tools/c4_host_stages.py).
-    const double t_frame = stage_now();
+    const double t_frame = now_ms();
     const uint32_t plen = (uint32_t)fr.prefix.size(), tl = (uint32_t)fr.trailer;
     std::vector<FrameItem> fi(m);
     std::vector<size_t> soff(m);
@@ -421,11 +317,11 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     for (size_t k = 0; k < m; ++k) {
       soff[k] = tot;
       fi[k] = FrameItem{oo[k], tot, (uint32_t)(oo[k + 1] - oo[k]), (uint32_t)len[k]};
-      tot += (plen + (oo[k + 1] - oo[k]) + tl + 64) & ~size_t(63);
+      tot += slab_stride(plen, oo[k + 1] - oo[k], tl);
     }
     const size_t fr_bytes = (tot + 255) & ~size_t(255), it_bytes = (m * sizeof(FrameItem) + 255) & ~size_t(255);
     void *d_fr;
-    if (int rc = scratch(c, kFramed, fr_bytes + it_bytes + plen + 256, &d_fr)) return fail(rc);
+    ZT_TRY(scratch(c, kFramed, fr_bytes + it_bytes + plen + 256, &d_fr));
     uint8_t *d_framed = static_cast<uint8_t *>(d_fr);
     FrameItem *d_items = reinterpret_cast<FrameItem *>(d_framed + fr_bytes);
     uint8_t *d_prefix = d_framed + fr_bytes + it_bytes;
@@ -435,22 +331,21 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
       ZT_HIP(hipEventRecord(c->aux_ev, c->aux));
       ZT_HIP(hipStreamWaitEvent(c->stream, c->aux_ev, 0));
     }
-    if (int rc = frame_members_dev(d_items, (uint32_t)m, d_prefix, plen,
-                                   fr.kind == Framing::GZIP ? 8u : fr.kind == Framing::ZLIB ? 4u : 0u,
-                                   static_cast<const uint8_t *>(d_out), static_cast<const uint32_t *>(d_sums),
-                                   d_framed, c->stream))
-      return fail(rc);
+    ZT_TRY(frame_members_dev(d_items, (uint32_t)m, d_prefix, plen,
+                             fr.kind == Framing::GZIP ? 8u : fr.kind == Framing::ZLIB ? 4u : 0u,
+                             static_cast<const uint8_t *>(d_out), static_cast<const uint32_t *>(d_sums), d_framed,
+                             c->stream));
     uint8_t *slab = slab_out(tot, m, true);
-    if (!slab) return fail(set_error(ZT_E_NOMEM, "host allocation failed"));
+    if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
     const bool direct = host_direct(slab, tot);
-    tm.frame_ms += stage_now() - t_frame;
+    tm.frame_ms += now_ms() - t_frame;
     if (direct) {  // (DMA time, not host work: like the upload, outside the stage timers)
       ZT_HIP(hipMemcpyAsync(slab, d_framed, tot, hipMemcpyDeviceToHost, c->stream));
       ZT_HIP(hipStreamSynchronize(c->stream));
     } else {
-      const double t_dl = stage_now();
-      if (int rc = download(c, slab, d_framed, tot, c->stream)) return fail(rc);
-      tm.frame_ms += stage_now() - t_dl;  // (staged: host copies)
+      const double t_dl = now_ms();
+      ZT_TRY(download(c, slab, d_framed, tot, c->stream));
+      tm.frame_ms += now_ms() - t_dl;  // (staged: host copies)
     }
     ZT_HIP(hipStreamSynchronize(c->aux));
     for (size_t k = 0; k < m; ++k) {
@@ -461,25 +356,25 @@ int batch_on_device(int dev, const uint8_t *const *in, const size_t *n, const st
     return ZT_OK;
   }
   ZT_HIP(hipStreamSynchronize(c->aux));
-  int first_rc = ZT_OK;
   std::vector<int> rcs(m, ZT_OK);
   std::vector<size_t> soff;
-  const double t_frame = stage_now();
+  const double t_frame = now_ms();
   uint8_t *slab = frame_slab(fr, oo.data(), m, soff);
-  if (!slab) return fail(set_error(ZT_E_NOMEM, "host allocation failed"));
+  if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
   parallel_copy(m, [&](size_t k) {
     const size_t i = work[k];
     rcs[k] = frame_item(fr, len[k], body_host + oo[k], oo[k + 1] - oo[k], hsums[2 * k], hsums[2 * k + 1], &out[i],
                         &out_len[i], slab + soff[k]);
   }, oo[m]);
-  tm.frame_ms += stage_now() - t_frame;
+  tm.frame_ms += now_ms() - t_frame;
   tm.out_bytes += oo[m];
   for (int rc : rcs)
-    if (rc && !first_rc) first_rc = rc;
-  return first_rc ? fail(first_rc) : ZT_OK;
+    if (rc) return rc;
+  return ZT_OK;
 }
 
-// split over the batch devices (LPT) and run every share on its own thread
+// split over the batch devices (LPT); a failed share fails the call: every
+// output is released and the first code and message are the caller's
 int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, int lv, const Framing &fr,
               uint8_t **out, size_t *out_len, int *status, const HostDict &hd = HostDict()) {
   for (size_t i = 0; i < count; ++i) {
@@ -487,52 +382,16 @@ int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, i
     out_len[i] = 0;
     if (n[i] && !in[i]) return set_error(ZT_E_ARG, "null input");
   }
-  const std::vector<int> devs = batch_devices();
-  const size_t nd = devs.size();
-  std::vector<std::vector<size_t>> share(nd);
-  if (nd == 1) {
-    share[0].resize(count);
-    for (size_t i = 0; i < count; ++i) share[0][i] = i;
-  } else {
-    std::vector<size_t> order(count);
-    for (size_t i = 0; i < count; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return n[a] > n[b]; });
-    std::vector<uint64_t> load(nd, 0);
-    for (size_t i : order) {
-      const size_t d = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-      share[d].push_back(i);
-      load[d] += n[i] + 4096;  // + per-item cost
-    }
-    for (auto &v : share) std::sort(v.begin(), v.end());
-  }
-  std::vector<int> rc(nd, ZT_OK);
-  std::vector<std::string> err(nd);
-  const int caller_dev = current_device();
-  if (nd == 1) {
-    rc[0] = batch_on_device(devs[0], in, n, share[0], ct, lv, fr, out, out_len, &err[0], hd);
-    zt_set_device(caller_dev);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < nd; ++d)
-      th.emplace_back([&, d] {
-        // the host's copy threads split between the device threads (8 per
-        // device thread put 64 on one GPU's 16-thread CPU share with 8
-        // devices; 32 in all packed fastest: slowest device's host stages
-        // 10.9 GiB/s with 16, 13.3 with 32, gpurun_out/r06ab);
-        // ZT_BATCH_COPY_THREADS overrides the total
-        static const size_t total = getenv("ZT_BATCH_COPY_THREADS") ? (size_t)atoi(getenv("ZT_BATCH_COPY_THREADS")) : 32;
-        set_copy_threads(std::max<size_t>(2, total / nd));
-        rc[d] = batch_on_device(devs[d], in, n, share[d], ct, lv, fr, out, out_len, &err[d], hd);
+  const std::vector<int> devs = fanout_devices(count);
+  const std::vector<std::vector<size_t>> share = lpt_shares(n, count, devs.size());
+  const std::vector<ShareResult> res =
+      for_each_device(devs, share, [&](size_t, DeviceCtx *c, const std::vector<size_t> &ids) {
+        return batch_on_device(c, in, n, ids, ct, lv, fr, out, out_len, hd);
       });
-    for (auto &t : th) t.join();
-  }
   int first = ZT_OK;
-  for (size_t d = 0; d < nd; ++d) {
-    for (size_t i : share[d]) status[i] = rc[d];
-    if (rc[d] && first == ZT_OK) {
-      first = rc[d];
-      set_error(rc[d], err[d]);
-    }
+  for (size_t d = 0; d < share.size(); ++d) {
+    for (size_t i : share[d]) status[i] = res[d].code;
+    if (res[d].code && first == ZT_OK) first = set_error(res[d].code, res[d].msg);
   }
   if (first) {
     for (size_t i = 0; i < count; ++i) {
@@ -542,18 +401,6 @@ int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, i
     }
   }
   return first;
-}
-
-int resolve_opts(const zt_deflate_opts *o, int *ct, int *lv) {
-  int c = o ? o->compression_type : 2;
-  int l = o ? o->level : -1;
-  if (c < 0 || c > 2) return set_error(ZT_E_INVALID_COMPRESSION_TYPE, "invalid compression type");
-  if (l < 0 || l > 9) l = 6;
-  if (l == 0) c = 0;
-  if (o && o->lazy > 0 && l < 4) l = 4;
-  *ct = c;
-  *lv = l;
-  return ZT_OK;
 }
 
 }  // namespace
@@ -606,22 +453,14 @@ int zt_crc32_batch(const uint8_t *const *in, const size_t *n, size_t count, uint
   DeviceCtx *c;
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-  std::vector<uint64_t> off(count), len(count);
-  uint64_t tot = 0;
-  for (size_t i = 0; i < count; ++i) {
+  for (size_t i = 0; i < count; ++i)
     if (n[i] && !in[i]) return set_error(ZT_E_ARG, "null input");
-    off[i] = tot;
-    len[i] = n[i];
-    tot += (n[i] + 255) & ~uint64_t(255);
-  }
-  void *d_in, *h, *d_sums;
-  ZT_TRY(scratch(c, kIn, tot + 64, &d_in));
-  ZT_TRY(pinned(c, tot + 64, &h, kPinBatch));
-  uint8_t *stage = static_cast<uint8_t *>(h);
-  parallel_copy(count, [&](size_t i) { copy_to_staging(stage + off[i], in[i], n[i]); }, tot);
-  ZT_HIP(hipMemcpyAsync(d_in, stage, tot ? tot : 1, hipMemcpyHostToDevice, c->stream));
+  const std::vector<size_t> ids = iota_ids(count);
+  const PackLayout L = pack_layout(n, ids, 256, 0);
+  void *d_in, *d_sums;
+  ZT_TRY(pack_upload(c, in, n, ids, L, PackMode{false, false}, &d_in));
   ZT_TRY(scratch(c, kSums, 8 * count, &d_sums));
-  ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in, count, off.data(), len.data(), (uint32_t *)d_sums, c->stream));
+  ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in, count, L.off.data(), n, (uint32_t *)d_sums, c->stream));
   std::vector<uint32_t> sums(2 * count);
   ZT_HIP(hipMemcpyAsync(sums.data(), d_sums, 8 * count, hipMemcpyDeviceToHost, c->stream));
   ZT_HIP(hipStreamSynchronize(c->stream));

@@ -19,18 +19,6 @@ namespace zt {
 
 namespace {
 
-int resolve_deflate(const zt_deflate_opts *o, int *ctype, int *level) {
-  int ct = o ? o->compression_type : 2;
-  int lv = o ? o->level : -1;
-  if (ct < 0 || ct > 2) return set_error(ZT_E_INVALID_COMPRESSION_TYPE, "invalid compression type");
-  if (lv < 0 || lv > 9) lv = 6;
-  if (lv == 0) ct = 0;
-  if (o && o->lazy > 0 && lv < 4) lv = 4;
-  *ctype = ct;
-  *level = lv;
-  return ZT_OK;
-}
-
 // Raw DEFLATE of host bytes into `out` after `prefix` bytes of header, with the
 // input's CRC-32 and/or Adler-32 from the same device copy of the input.
 // *out (malloc'd) = prefix | stream | `trailer` bytes of room.
@@ -41,8 +29,8 @@ int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *o
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   int ct, lv;
-  ZT_TRY(resolve_deflate(opts, &ct, &lv));
-  const size_t ob = (ct == 0 ? n + 5 * ((n + 65534) / 65535) + 16 : deflate_bound_bytes(n) + (ct == 1 ? n / 8 + 64 : 0));
+  ZT_TRY(resolve_opts(opts, &ct, &lv));
+  const size_t ob = deflate_out_bound(ct, n);
   void *d_in, *d_out, *d_scr, *d_res;
   ZT_TRY(scratch(c, kIn, n + 64, &d_in));
   ZT_TRY(scratch(c, kOut, ob, &d_out));
@@ -53,10 +41,7 @@ int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *o
   // the checksums run on the second stream beside the deflate pipeline (both
   // only read the input); every return below waits for that stream first
   uint32_t sums[2] = {0, 1};  // CRC-32 and Adler-32 of nothing
-  struct AuxWait {
-    hipStream_t s;
-    ~AuxWait() { (void)hipStreamSynchronize(s); }
-  } aux_wait{c->aux};
+  AuxWait aux_wait{c->aux};
   if (n) {
     ZT_HIP(hipEventRecord(c->aux_ev, c->stream));
     ZT_HIP(hipStreamWaitEvent(c->aux, c->aux_ev, 0));

@@ -28,7 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/zt_container_batch.h"
@@ -66,30 +65,13 @@ std::string inflate_message(int status, int detail) {
 }
 
 // items `ids` packed at 256-byte offsets into scratch slot kIn, uploaded in
-// chunks of about 32 MiB as they are packed
-int pack_upload(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids,
-                std::vector<size_t> &in_off, size_t *total, void **d_in) {
-  const size_t m = ids.size();
-  in_off.resize(m);
-  size_t tot = 0;
-  for (size_t k = 0; k < m; ++k) {
-    in_off[k] = tot;
-    tot += align_up(n[ids[k]] ? n[ids[k]] : 1, 256);
-  }
-  *total = tot;
-  ZT_TRY(scratch(c, kIn, tot + 64, d_in));
-  void *h;
-  ZT_TRY(pinned(c, tot, &h));
-  uint8_t *stage = static_cast<uint8_t *>(h);
-  constexpr size_t kChunk = 32u << 20;
-  for (size_t a = 0; a < m;) {
-    size_t b = a + 1;
-    while (b < m && in_off[b] - in_off[a] < kChunk) ++b;
-    const size_t lo = in_off[a], hi = b < m ? in_off[b] : tot;
-    parallel_copy(b - a, [&](size_t k) { copy_to_staging(stage + in_off[a + k], in[ids[a + k]], n[ids[a + k]]); }, tot);
-    ZT_HIP(hipMemcpyAsync(static_cast<uint8_t *>(*d_in) + lo, stage + lo, hi - lo, hipMemcpyHostToDevice, c->stream));
-    a = b;
-  }
+// chunks as they are packed
+int pack_in(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids,
+            std::vector<size_t> &in_off, size_t *total, void **d_in) {
+  PackLayout L = pack_layout(n, ids, 256, 1);
+  ZT_TRY(pack_upload(c, in, n, ids, L, PackMode{false, true}, d_in));
+  in_off.swap(L.off);
+  *total = L.total;
   return ZT_OK;
 }
 
@@ -111,7 +93,7 @@ int gunzip_share_locked(DeviceCtx *c, const GunzipArgs &A, const std::vector<siz
   std::vector<size_t> in_off;
   size_t total = 0;
   void *d_in;
-  ZT_TRY(pack_upload(c, A.in, A.n, ids, in_off, &total, &d_in));
+  ZT_TRY(pack_in(c, A.in, A.n, ids, in_off, &total, &d_in));
   // candidates: the list's capacity is proportional to the packed input (one
   // per item and per 256 bytes; gz_slack keeps the decode scratch in proportion)
   const uint32_t cap = (uint32_t)std::min<size_t>(m + total / 256, 0x7FFFFFFFu);
@@ -281,7 +263,7 @@ int gunzip_share_locked(DeviceCtx *c, const GunzipArgs &A, const std::vector<siz
     const GzWalk &w = walk[k];
     if (w.state == GZ_FAILED || w.members.size() < 2) continue;
     join_off[k] = join_total;
-    join_total += (w.total + 64) & ~size_t(63);  // (>= 1 byte each: every pointer distinct)
+    join_total += slab_stride(0, w.total, 0);  // (>= 1 byte each: every pointer distinct)
     ++join_items;
   }
   uint8_t *jslab = join_items ? slab_out(join_total, join_items, true) : nullptr;
@@ -388,7 +370,7 @@ int zlib_share_locked(DeviceCtx *c, const ZlibArgs &A, const std::vector<size_t>
   std::vector<size_t> in_off;
   size_t total = 0;
   void *d_in;
-  ZT_TRY(pack_upload(c, A.in, A.n, ids, in_off, &total, &d_in));
+  ZT_TRY(pack_in(c, A.in, A.n, ids, in_off, &total, &d_in));
   const uint8_t *d_hist = nullptr;
   uint32_t wlen = 0;
   if (!part[1].empty()) {  // this device's copy of the dictionary's window
@@ -451,63 +433,20 @@ int zlib_share_locked(DeviceCtx *c, const ZlibArgs &A, const std::vector<size_t>
 }
 
 // ---- devices ----------------------------------------------------------------------
-// Items split over the batch devices by longest processing time (largest first
-// onto the least loaded device); share(dev index, device context, ids) runs on
-// its own thread with that device current and its context locked.  A share
-// that fails as a whole gives its code and message to each of its items.
+// Items split over the batch devices by longest processing time; share(dev
+// index, device context, ids) runs under for_each_device.  A share that fails
+// as a whole gives its code and message to each of its items.
 template <class Share>
-int run_shares(const size_t *n, size_t count, int *status, std::string *msgs, const Share &share) {
-  const std::vector<int> devs = batch_devices();
-  const size_t nd = std::max<size_t>(1, std::min(devs.size(), count));
-  std::vector<std::vector<size_t>> ids(nd);
-  if (nd == 1) {
-    ids[0].resize(count);
-    for (size_t i = 0; i < count; ++i) ids[0][i] = i;
-  } else {
-    std::vector<size_t> order(count);
-    for (size_t i = 0; i < count; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return n[a] > n[b]; });
-    std::vector<uint64_t> load(nd, 0);
-    for (size_t i : order) {
-      const size_t d = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
-      ids[d].push_back(i);
-      load[d] += n[i] + 4096;  // + per-item cost
-    }
-    for (auto &v : ids) std::sort(v.begin(), v.end());
-  }
-  std::vector<int> rc(nd, ZT_OK);
-  std::vector<std::string> err(nd);
-  const int caller_dev = current_device();
-  auto one = [&](size_t d) {
-    auto fail = [&](int code) {
-      err[d] = zt_last_error_message();
-      rc[d] = code;
-    };
-    if (zt_set_device(devs[d])) return fail(ZT_E_NO_DEVICE);
-    DeviceCtx *c;
-    if (int r = get_ctx(&c)) return fail(r);
-    std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-    if (int r = share(d, c, ids[d])) fail(r);
-  };
-  if (nd == 1) {
-    one(0);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < nd; ++d)
-      th.emplace_back([&, d] {
-        set_copy_threads(std::max<size_t>(2, 32 / nd));  // (the host's copy threads split between the device threads)
-        one(d);
-      });
-    for (auto &t : th) t.join();
-  }
-  zt_set_device(caller_dev);
-  for (size_t d = 0; d < nd; ++d)
-    if (rc[d])
+void run_shares(const size_t *n, size_t count, int *status, std::string *msgs, const Share &share) {
+  const std::vector<int> devs = fanout_devices(count);
+  const std::vector<std::vector<size_t>> ids = lpt_shares(n, count, devs.size());
+  const std::vector<ShareResult> res = for_each_device(devs, ids, share);
+  for (size_t d = 0; d < ids.size(); ++d)
+    if (res[d].code)
       for (size_t i : ids[d]) {
-        status[i] = rc[d];
-        msgs[i] = err[d];
+        status[i] = res[d].code;
+        msgs[i] = res[d].msg;
       }
-  return ZT_OK;
 }
 
 // first failing item's code with its message set; this thread's messages
@@ -538,7 +477,7 @@ int zlib_batch(const uint8_t *const *in, const size_t *n, const size_t *index, s
   if (dict_len) ZT_TRY(zt_adler32_update(1, dict, dict_len, &dictid));  // (the checksum kernel, over the whole dictionary)
   std::vector<std::string> msgs(count);
   const ZlibArgs A{in, n, index, verify, dict, dict_len, dictid, out, out_len, end_ip, adler_out, status, msgs.data()};
-  ZT_TRY(run_shares(n, count, status, msgs.data(), [&](size_t, DeviceCtx *c, const std::vector<size_t> &ids) {
+  run_shares(n, count, status, msgs.data(), [&](size_t, DeviceCtx *c, const std::vector<size_t> &ids) {
     const int rc = zlib_share_locked(c, A, ids);
     if (rc)  // (the share failed as a whole: nothing of it is handed out)
       for (size_t i : ids) {
@@ -547,7 +486,7 @@ int zlib_batch(const uint8_t *const *in, const size_t *n, const size_t *index, s
         out_len[i] = 0;
       }
     return rc;
-  }));
+  });
   return finish(count, status, msgs);
 }
 
@@ -577,7 +516,7 @@ int zt_gunzip_batch(const uint8_t *const *in, const size_t *n, size_t count, uin
   std::vector<std::string> msgs(count);
   const GunzipArgs A{in, n, out, out_len, members, nmembers, status, msgs.data()};
   std::vector<zt_gunzip_batch_stats> st(batch_devices().size() + 1, zt_gunzip_batch_stats{0, 0, 0, 0, 0});
-  ZT_TRY(run_shares(n, count, status, msgs.data(), [&](size_t d, DeviceCtx *c, const std::vector<size_t> &ids) {
+  run_shares(n, count, status, msgs.data(), [&](size_t d, DeviceCtx *c, const std::vector<size_t> &ids) {
     const int rc = gunzip_share_locked(c, A, ids, &st[d]);
     if (rc)  // (the share failed as a whole: nothing of it is handed out)
       for (size_t i : ids) {
@@ -591,7 +530,7 @@ int zt_gunzip_batch(const uint8_t *const *in, const size_t *n, size_t count, uin
         if (nmembers) nmembers[i] = 0;
       }
     return rc;
-  }));
+  });
   for (const zt_gunzip_batch_stats &s : st) {
     t_stats.candidates += s.candidates;
     t_stats.members += s.members;

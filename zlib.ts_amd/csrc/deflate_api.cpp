@@ -7,28 +7,6 @@
 
 #include "zt_internal.h"
 
-namespace zt {
-
-static int resolve(const zt_deflate_opts *o, int *ctype, int *level) {
-  int ct = o ? o->compression_type : 2;
-  int lv = o ? o->level : -1;
-  if (ct < 0 || ct > 2) return set_error(ZT_E_INVALID_COMPRESSION_TYPE, "invalid compression type");
-  if (lv < 0 || lv > 9) lv = 6;
-  if (lv == 0) ct = 0;
-  // the reference's `lazy` option asks for deferred matching: use the lazy parse
-  if (o && o->lazy > 0 && lv < 4) lv = 4;
-  *ctype = ct;
-  *level = lv;
-  return ZT_OK;
-}
-
-static size_t out_bound(int ctype, size_t n) {
-  if (ctype == 0) return n + 5 * ((n + 65534) / 65535) + 16;
-  return deflate_bound_bytes(n) + (ctype == 1 ? n / 8 + 64 : 0);
-}
-
-}  // namespace zt
-
 using namespace zt;
 
 struct zt_deflate_plan {
@@ -47,7 +25,7 @@ struct zt_inflate_plan {
 
 extern "C" {
 
-size_t zt_deflate_bound(size_t n) { return out_bound(1, n) + out_bound(0, n); }
+size_t zt_deflate_bound(size_t n) { return deflate_out_bound(1, n) + deflate_out_bound(0, n); }
 
 int zt_deflate_plan_create(size_t max_n, const zt_deflate_opts *opts, zt_deflate_plan **plan) {
   if (!plan) return set_error(ZT_E_ARG, "null plan");
@@ -55,7 +33,7 @@ int zt_deflate_plan_create(size_t max_n, const zt_deflate_opts *opts, zt_deflate
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   int ct, lv;
-  ZT_TRY(resolve(opts, &ct, &lv));
+  ZT_TRY(resolve_opts(opts, &ct, &lv));
   zt_deflate_plan *p = new zt_deflate_plan();
   p->device = c->device;
   p->ctype = ct;
@@ -150,7 +128,7 @@ static int deflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, int 
   size_t pmax = 0;
   for (size_t i = 0; i < np; ++i) {
     in_off[i + 1] = in_off[i] + sizes[i];
-    out_off[i + 1] = out_off[i] + ((out_bound(ct, sizes[i]) + 255) & ~(size_t)255);
+    out_off[i + 1] = out_off[i] + ((deflate_out_bound(ct, sizes[i]) + 255) & ~(size_t)255);
     pmax = std::max(pmax, sizes[i]);
   }
   void *d_in, *d_out, *d_scr;
@@ -190,9 +168,9 @@ int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uin
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   int ct, lv;
-  ZT_TRY(resolve(opts, &ct, &lv));
+  ZT_TRY(resolve_opts(opts, &ct, &lv));
   if (ct != 0 && n >= kPipeMin) return deflate_raw_pipelined(c, in, n, ct, lv, out, out_len);
-  const size_t ob = out_bound(ct, n);
+  const size_t ob = deflate_out_bound(ct, n);
   void *d_in, *d_out, *d_scr;
   ZT_TRY(scratch(c, kIn, n + 64, &d_in));
   ZT_TRY(scratch(c, kOut, ob, &d_out));

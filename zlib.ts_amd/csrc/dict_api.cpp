@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/zt_dict.h"
@@ -20,71 +19,41 @@ using namespace zt;
 
 namespace {
 
-// streams [i0, i1) of the batch on device `dev` (this thread's afterwards)
-int inflate_share(int dev, const uint8_t *const *in, const size_t *n, const size_t *index, size_t i0, size_t i1,
-                  const uint8_t *dict, size_t dict_len, uint8_t **out, size_t *out_len, size_t *end_ip, int *status,
-                  std::string *err) {
-  auto fail = [&](int rc) {
-    *err = zt_last_error_message();
-    return rc;
-  };
-  if (zt_set_device(dev)) return fail(ZT_E_NO_DEVICE);
-  DeviceCtx *c;
-  if (int rc = get_ctx(&c)) return fail(rc);
-  std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+// streams [i0, i1) of the batch on the locked context c (for_each_device)
+int inflate_share(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const size_t *index, size_t i0, size_t i1,
+                  const uint8_t *dict, size_t dict_len, uint8_t **out, size_t *out_len, size_t *end_ip, int *status) {
   const uint32_t wlen = dict_window_len(dict_len);
   void *d_hist;
-  if (int rc = scratch(c, kDict, wlen, &d_hist)) return fail(rc);
+  ZT_TRY(scratch(c, kDict, wlen, &d_hist));
   if (hipMemcpyAsync(d_hist, dict + dict_window_off(dict_len), wlen, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
-    return fail(set_error(ZT_E_HIP, "dictionary upload failed"));
-  const int rc = inflate_host_batch_hist(in + i0, n + i0, index ? index + i0 : nullptr, i1 - i0,
-                                         static_cast<const uint8_t *>(d_hist), wlen, out + i0, out_len + i0,
-                                         end_ip ? end_ip + i0 : nullptr, status + i0);
-  return rc ? fail(rc) : ZT_OK;
+    return set_error(ZT_E_HIP, "dictionary upload failed");
+  return inflate_host_batch_hist(in + i0, n + i0, index ? index + i0 : nullptr, i1 - i0,
+                                 static_cast<const uint8_t *>(d_hist), wlen, out + i0, out_len + i0,
+                                 end_ip ? end_ip + i0 : nullptr, status + i0);
 }
 
-int inflate_batch_dict(const uint8_t *const *in, const size_t *n, const size_t *index, size_t count,
-                       const uint8_t *dict, size_t dict_len, uint8_t **out, size_t *out_len, size_t *end_ip,
-                       int *status) {
+// the batch over `devs`: contiguous shares of about equal compressed bytes
+// (inflate_host_batch_hist takes a range); the first failed share's code and message
+int inflate_batch_dict(const std::vector<int> &devs, const uint8_t *const *in, const size_t *n, const size_t *index,
+                       size_t count, const uint8_t *dict, size_t dict_len, uint8_t **out, size_t *out_len,
+                       size_t *end_ip, int *status) {
   for (size_t i = 0; i < count; ++i) {
     out[i] = nullptr;
     out_len[i] = 0;
     status[i] = ZT_OK;
     if (n[i] && !in[i]) return set_error(ZT_E_ARG, "null input");
   }
-  const std::vector<int> devs = batch_devices();
-  const size_t nd = std::min(devs.size(), count);
-  const int caller_dev = current_device();
-  std::vector<int> rc(nd, ZT_OK);
-  std::vector<std::string> err(nd);
-  // contiguous shares of about equal compressed bytes
-  std::vector<size_t> cut(nd + 1, count);
-  cut[0] = 0;
-  if (nd > 1) {
-    uint64_t total = 0, acc = 0;
-    for (size_t i = 0; i < count; ++i) total += n[i] + 256;
-    size_t d = 1;
-    for (size_t i = 0; i < count && d < nd; ++i) {
-      acc += n[i] + 256;
-      if (acc * nd >= total * d) cut[d++] = i + 1;
-    }
-  }
-  if (nd == 1) {
-    rc[0] = inflate_share(devs[0], in, n, index, 0, count, dict, dict_len, out, out_len, end_ip, status, &err[0]);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t d = 0; d < nd; ++d)
-      th.emplace_back([&, d] {
-        if (cut[d] < cut[d + 1])
-          rc[d] = inflate_share(devs[d], in, n, index, cut[d], cut[d + 1], dict, dict_len, out, out_len, end_ip,
-                                status, &err[d]);
+  const std::vector<size_t> cut = contiguous_cuts(n, count, devs.size());
+  std::vector<std::vector<size_t>> shares(devs.size());
+  for (size_t d = 0; d < devs.size(); ++d)
+    for (size_t i = cut[d]; i < cut[d + 1]; ++i) shares[d].push_back(i);
+  const std::vector<ShareResult> res =
+      for_each_device(devs, shares, [&](size_t d, DeviceCtx *c, const std::vector<size_t> &) {
+        return inflate_share(c, in, n, index, cut[d], cut[d + 1], dict, dict_len, out, out_len, end_ip, status);
       });
-    for (auto &t : th) t.join();
-  }
-  zt_set_device(caller_dev);
-  for (size_t d = 0; d < nd; ++d)
-    if (rc[d]) return set_error(rc[d], err[d]);
+  for (const ShareResult &r : res)
+    if (r.code) return set_error(r.code, r.msg);
   return ZT_OK;
 }
 
@@ -142,7 +111,8 @@ int zt_inflate_raw_batch_dict(const uint8_t *const *in, const size_t *n, size_t 
   if (dict_len == 0) return zt_inflate_raw_batch(in, n, count, opts, out, out_len, end_ip, status);
   if (count == 0) return ZT_OK;
   if (!in || !n || !out || !out_len || !status || !dict) return set_error(ZT_E_ARG, "null argument");
-  return inflate_batch_dict(in, n, nullptr, count, dict, dict_len, out, out_len, end_ip, status);
+  return inflate_batch_dict(fanout_devices(count), in, n, nullptr, count, dict, dict_len, out, out_len, end_ip,
+                            status);
 }
 
 int zt_inflate_raw_dict(const uint8_t *in, size_t n, size_t index, const zt_inflate_opts *opts, const uint8_t *dict,
@@ -153,9 +123,7 @@ int zt_inflate_raw_dict(const uint8_t *in, size_t n, size_t index, const zt_infl
   int st = 0;
   size_t ip = 0;
   // (one stream: the current device, whatever zt_set_devices says)
-  std::string err;
-  const int rc = inflate_share(current_device(), &in, &n, &index, 0, 1, dict, dict_len, out, out_len, &ip, &st, &err);
-  if (rc) return set_error(rc, err);
+  ZT_TRY(inflate_batch_dict({current_device()}, &in, &n, &index, 1, dict, dict_len, out, out_len, &ip, &st));
   if (end_ip) *end_ip = ip;
   return ZT_OK;
 }

@@ -1,5 +1,6 @@
 // zt_internal.h -- shared host/device helpers for libzt (not installed).
 #pragma once
+#include <condition_variable>
 #include <functional>
 #include <mutex>
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/zt.h"
+#include "batch_plan.h"
 #include "dict_host.h"
 #include "inflate_chain.h"
 
@@ -157,7 +159,8 @@ class Carve {
 // Host wall-clock stamps of a host driver's stages on stderr when the
 // environment variable `env` is set (measurement only): ZT_INF_TIMING in
 // inflate_seg.hip, ZT_BATCH_TIMING in inflate_api.cpp.
-void host_stamp(const char *tag, const char *label);  // zt_api.cpp: "[tag] label  <ms since the epoch>"
+double now_ms();                                      // the host's steady clock, in milliseconds
+void host_stamp(const char *tag, const char *label);  // "[tag] label  <now_ms()>"
 #define ZT_STAMP(env, tag, label)                   \
   do {                                              \
     static const bool on_ = getenv(env) != nullptr; \
@@ -206,7 +209,7 @@ int q_bytes(void *dst, uint64_t v, uint32_t n, hipStream_t s);
 int mailbox(DeviceCtx *c, size_t n, void **p);
 int readback(DeviceCtx *c, void *h_dst, const void *d_src, size_t n, hipStream_t s);
 // Host output buffer the caller frees with zt_free (large ones on huge pages;
-// pool = true: from the bounded host output pool, zt_api.cpp); host_release
+// pool = true: from the bounded host output pool, host_mem.cpp); host_release
 // is zt_free's second half (back to the pool, or free).  host_direct: [p,
 // p + n) lies in a pool buffer registered with HIP, so copies to / from it go
 // by DMA without staging.
@@ -218,6 +221,7 @@ void host_release(void *p);
 void host_out_used(void *p, size_t n);
 void host_discard(void *p);
 bool host_direct(const void *p, size_t n);
+void host_pool_drop();  // the pool's free buffers released (zt_release_scratch)
 // One host allocation for `items` batch outputs (pointers inside it, each
 // released by zt_free; reserve >= 1 byte per item so every pointer is
 // distinct).  slab_release: true when p lay in a slab (and was released).
@@ -235,7 +239,7 @@ int frame_members_dev(const FrameItem *d_items, uint32_t count, const uint8_t *d
                       uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s);
 bool slab_release(void *p);
 // fn(0 .. count-1) over a few host threads when total_bytes is large.
-// memcpy into pinned staging with streaming stores (zt_api.cpp)
+// memcpy into pinned staging with streaming stores (xfer.cpp)
 void copy_to_staging(void *dst, const void *src, size_t n);
 void parallel_copy(size_t count, const std::function<void(size_t)> &fn, size_t total_bytes);
 // parallel_copy's thread budget on the calling thread (default 8)
@@ -460,7 +464,7 @@ int checksums_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, bool do_crc, bool
 int checksums_batch_dev(DeviceCtx *c, const uint8_t *frame, size_t count, const uint64_t *off, const uint64_t *len,
                         uint32_t *d_result /* [2 count] */, hipStream_t s);
 void gzip_header(const zt_gzip_opts *opts, std::vector<uint8_t> &hd);  // container_api.cpp
-int current_device();                                                 // zt_api.cpp (this thread's)
+int current_device();                                                 // this thread's (zt_set_device)
 std::vector<int> batch_devices();                                     // zt_set_devices, else {current}
 // debug (deflate.hip; exported, not part of include/zt.h): blocks of the
 // match kernel that measured their candidates through the queues (out[0]) and
@@ -791,6 +795,80 @@ struct PipeOut {
 };
 int pipeline_h2d_d2h(DeviceCtx *c, size_t np, const std::function<PipePiece(size_t)> &input,
                      const std::function<int(size_t, const void **d_res, size_t *n_res)> &compute, PipeOut &out);
+// The skeleton of a three-stage host pipeline over np pieces (xfer.cpp): run()
+// calls up(i) and dn(i) in order on a thread each (the context's device
+// current) and compute(i) on the caller's.  up(i) enqueues piece i's upload
+// on c->up; the pipeline records landed(i) behind it and makes c->stream wait
+// for it before compute(i); dn(i) runs once compute(i) has returned.  The
+// first stage to fail stops the others, and its code and message are the
+// caller's (zt_last_error_message() on the caller's thread).  On every
+// return after the threads started, c->up, c->dn, c->aux and c->stream are
+// drained: nothing still reads the caller's input or staging, or writes its
+// output.  Users: pipeline_h2d_d2h, the grouped batch (batch_api.cpp).
+class StagePipe {
+ public:
+  typedef std::function<int(size_t)> Stage;
+  StagePipe(DeviceCtx *c, size_t np) : c_(c), np_(np) {}
+  ~StagePipe();
+  int run(const Stage &up, const Stage &compute, const Stage &dn);
+  hipEvent_t landed(size_t i) const { return landed_[i]; }
+  // waits until dn(j) has returned; false: the pipeline stopped
+  bool wait_downloaded(size_t j) { return wait(downloaded_, j); }
+  std::function<void(const char *)> trace;  // "joined", "drained" (measurement only)
+
+ private:
+  void fail(int rc);
+  bool stopped();
+  bool wait(const size_t &counter, size_t i);
+  void done(size_t &counter, size_t i);
+  DeviceCtx *c_;
+  size_t np_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  // pieces whose upload is enqueued / whose result is on the device / whose
+  // download stage has returned
+  size_t uploaded_ = 0, computed_ = 0, downloaded_ = 0;
+  int err_ = 0;
+  std::string err_msg_;
+  std::vector<hipEvent_t> landed_;
+};
+
+// ---- the host batch layer (host_batch.cpp; its arithmetic: batch_plan.h) ----------
+// Waits for a stream on every return of its scope (the checksums on c->aux
+// beside a deflate pipeline: both read the input, so neither may outlive it)
+struct AuxWait {
+  hipStream_t s;
+  ~AuxWait() { (void)hipStreamSynchronize(s); }
+};
+inline size_t deflate_out_bound(int ctype, size_t n) { return deflate_out_bound(ctype, n, deflate_bound_bytes(n)); }
+// resolve_deflate_opts with the reference's message set
+int resolve_opts(const zt_deflate_opts *o, int *ctype, int *level);
+// The batch devices a call of `count` items spreads over: the first
+// min(devices, count) of batch_devices(), at least one.
+std::vector<int> fanout_devices(size_t count);
+// fn(d, context of devs[d], shares[d]) for every non-empty share: on the
+// caller's thread when there is one share, else on a thread each, with that
+// device current and its context locked.  Each share's code and -- read in
+// one place, on its thread -- message come back; the caller's device is
+// restored.  With several shares the host's copy threads (parallel_copy;
+// ZT_BATCH_COPY_THREADS in all, default 32) are split between the threads.
+std::vector<ShareResult> for_each_device(const std::vector<int> &devs, const std::vector<std::vector<size_t>> &shares,
+                                         const std::function<int(size_t, DeviceCtx *, const std::vector<size_t> &)> &fn);
+// Items `ids` of (in, n) packed by layout L (pack_layout) into the pinned batch
+// staging and uploaded to scratch slot kIn (*d_in) on c->stream: in chunks of
+// about 32 MiB as they are packed (the copy engine moves chunk k while the
+// host packs chunk k + 1), or all at once.
+struct PackMode {
+  bool zero_pad;   // the bytes between an item's end and the next 32 KiB boundary zeroed (L aligned to 32768)
+  bool chunked;
+  size_t copy_bytes = 0;      // parallel_copy's thread budget; 0: L.total
+  double *pack_ms = nullptr;  // += the host's packing time
+};
+int pack_upload(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids,
+                const PackLayout &L, const PackMode &mode, void **d_in);
+// the packing alone: items [a, b) of the layout to stage + L.off[k] - L.off[a]
+void pack_items(uint8_t *stage, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids,
+                const PackLayout &L, size_t a, size_t b, bool zero_pad, size_t copy_bytes);
 int inflate_error(int status, int detail);
 
 }  // namespace zt
