@@ -35,6 +35,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/warp/warp_scan.hpp>
 
+#include "index_host.h"
 #include "zt_internal.h"
 
 namespace zt {
@@ -57,6 +58,7 @@ bool inf_debug() {
 // (zt_internal.h): <= 1 token per byte
 constexpr uint32_t kUnitTokCap = DF_BLOCK * DF_GROUP + 64;
 static_assert(kUnitTokCap < (1u << 30), "token counts stay below TokResult::ntok's flag bits");
+static_assert(kUnitTokCap == kIdxUnitTokCap, "the index validation's bound is the unit token capacity");
 
 // sync point = byte after an aligned 00 00 FF FF; list entry = pos << 1 | restart
 // One 16-byte aligned chunk per lane, loaded as one 16-byte word; the 8 bytes
@@ -577,6 +579,30 @@ __global__ void unit_starts_at(const TokJob *__restrict__ jobs, uint32_t units, 
     if (jobs[u].start == pos) atomicOr(flag, 1u);
 }
 
+// The index entries (index_host.h: IdxEntry) of a proven chain, one lane per
+// unit: chain unit k is unit on_chain[k] of the tables (null: unit k, the
+// device-built chain, which holds every unit); entry nchain is the sentinel.
+__global__ __launch_bounds__(256) void index_pack_kernel(const TokJob *__restrict__ jobs,
+                                                         const TokResult *__restrict__ res,
+                                                         const uint8_t *__restrict__ restart,
+                                                         const ChainUnit *__restrict__ cu,
+                                                         const uint32_t *__restrict__ on_chain, uint32_t nchain,
+                                                         uint64_t end_ip, uint64_t total, IdxEntry *__restrict__ out) {
+  const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+  if (k > nchain) return;
+  IdxEntry e;
+  if (k == nchain) {
+    e = IdxEntry{end_ip, total, 0u, 0u};
+  } else {
+    const uint32_t u = on_chain ? on_chain[k] : k;
+    e.in_off = jobs[u].start;
+    e.out_off = cu[k].out_off;
+    e.ntok = res[u].ntok & 0x3FFFFFFFu;
+    e.flags = (u == 0 || restart[u - 1] != 0) ? 1u : 0u;
+  }
+  out[k] = e;
+}
+
 namespace {
 
 // room behind a device chain's statuses: its ChainInfo and the boundary flag
@@ -838,6 +864,7 @@ struct SegCall {
   size_t *out_len, *end_ip;
   hipStream_t s;
   uint64_t boundary;
+  std::vector<uint8_t> *index_blob = nullptr;  // the index build: receives the blob once the chain is proven
 };
 
 int seg_done(const SegCall &a, const ChainRun &run, const char *tag) {
@@ -926,6 +953,36 @@ int seg_chain_device(const SegCall &a, const SegUnits &U, const uint32_t *d_tok,
   return ZT_OK;
 }
 
+// the index of a chain that expand and copy have proved (no error, no match
+// behind a segment start): packed on the device from the unit tables and the
+// chain, one table back
+int seg_index_pack(const SegCall &a, const SegUnits &U, const ChainPlan &plan, const ChainRun &run) {
+  DeviceCtx *c = a.c;
+  hipStream_t s = a.s;
+  const size_t nchain = plan.chain.size();
+  uint32_t *d_on = nullptr;
+  IdxEntry *d_ent = nullptr;
+  ZT_TRY(scratch_carved(c, kIndexPack, [&](void *base) {
+    Carve cv(base);
+    d_on = cv.take<uint32_t>(nchain);
+    d_ent = cv.take<IdxEntry>(nchain + 1);
+    return cv.bytes();
+  }));
+  ZT_HIP(hipMemcpyAsync(d_on, plan.on_chain.data(), nchain * 4, hipMemcpyHostToDevice, s));
+  index_pack_kernel<<<(uint32_t)((nchain + 1 + 255) / 256), 256, 0, s>>>(U.d_jobs, U.d_res, U.d_restart, run.dev.units,
+                                                                        d_on, (uint32_t)nchain, *a.end_ip, *a.out_len,
+                                                                        d_ent);
+  ZT_HIP(hipGetLastError());
+  std::vector<uint8_t> &blob = *a.index_blob;
+  blob.assign(index_blob_bytes(nchain), 0);
+  ZT_TRY(readback(c, blob.data() + kIdxHeader, d_ent, (nchain + 1) * sizeof(IdxEntry), s));
+  uint32_t nseg = 0;
+  for (size_t k = 0; k < nchain; ++k) nseg += idx_get32(blob.data() + kIdxHeader + k * kIdxEntry + 20) & 1u;
+  index_write_header(blob.data(), (uint32_t)nchain, nseg, idx_get64(blob.data() + kIdxHeader), *a.end_ip, *a.out_len);
+  IT("index packed");
+  return ZT_OK;
+}
+
 // 3b-4. the unit tables back to the host, the chain walked there
 // (seg_chain_host), then expand (one wave per unit) and copy (one wave per
 // segment)
@@ -983,7 +1040,9 @@ int seg_chain_on_host(const SegCall &a, const SegUnits &U, const uint32_t *d_tok
   ZT_TRY(timing_end(c, s, 2));
   ZT_TRY(chain_statuses(run, s));
   IT("resolved");
-  return seg_done(a, run, "chain");
+  const int done = seg_done(a, run, "chain");
+  if (done != ZT_OK || !a.index_blob) return done;
+  return seg_index_pack(a, U, plan, run);
 }
 
 }  // namespace
@@ -1002,6 +1061,21 @@ int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t ind
   bool resolved;
   const int rc = seg_chain_device(a, U, d_tok, pin, /*plain=*/!d_dbg && !inf_debug(), &resolved);
   if (rc || resolved) return rc;
+  return seg_chain_on_host(a, U, d_tok, pin, d_dbg);
+}
+
+int inflate_index_build_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out,
+                            size_t *out_len, size_t *end_ip, std::vector<uint8_t> *blob, hipStream_t s) {
+  IT("index build start");
+  if (n <= index) return 1;
+  SegUnits U;
+  ZT_TRY(seg_find_units(c, d_in, n, index, s, &U));
+  uint32_t *d_tok;
+  SegPinned pin;
+  uint64_t *d_dbg;
+  ZT_TRY(seg_tokenize(c, d_in, n, U, s, &d_tok, &pin, &d_dbg));
+  *d_out = nullptr;  // library-owned
+  const SegCall a{c, d_in, n, d_out, 0, out_len, end_ip, s, ~0ull, blob};
   return seg_chain_on_host(a, U, d_tok, pin, d_dbg);
 }
 

@@ -87,6 +87,10 @@ enum ScratchSlot : int {
   kTokOrder = 28,   // segment path: tokenize / expand launch order, up to resolve
   kDict = 29,       // a preset dictionary (zt_dict.h: deflate history | inflate window | the whole dictionary);
                     // the holder may call the batch deflate / inflate launchers
+  kIndexPack = 30,  // index build (inflate_seg.hip): on-chain unit ids | packed index entries; after resolve, inside the call
+  kRangeIn = 31,    // range inflate (index_api.hip): stops | TokJob | chain | segments | ranges | ChainInfo |
+                    // packed input (one upload), then TokResult; whole call (it also takes kTokens, kDeflateOrDesc and kOut)
+  kRangeOut = 32,   // range inflate: packed ranges | statuses, one download; whole call
   kScratchSlots
 };
 // Pinned host staging (DeviceCtx::h_pinned, pinned()).
@@ -581,6 +585,14 @@ struct InfResult {
 // real block boundary of the whole stream)
 int inflate_segments_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
                          size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s, uint64_t boundary = ~0ull);
+// The index build (include/zt_index.h): the stages of inflate_segments_dev
+// with no minimum stream size, the chain always walked on the host and the
+// output library-owned (kOut, returned in *d_out); after expand and copy have
+// proved the chain, index_pack_kernel packs the on-chain units and *blob
+// receives the finished index.  Returns 0, 1 or 2 (the stream is off the
+// sync-point path: no index) or a negative status.
+int inflate_index_build_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out,
+                            size_t *out_len, size_t *end_ip, std::vector<uint8_t> *blob, hipStream_t s);
 // The large-stream cascade (inflate_api.cpp): the segment path, then -- unless
 // allow_general is false or the segment path returned 2 (its chain ran out of
 // input: the general path cannot finish either) -- the general path.  A

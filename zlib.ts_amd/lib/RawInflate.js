@@ -3,7 +3,7 @@
 // buffer, output); decoding runs in libzt on the GPU (zt_inflate_raw).
 // `refStrict: true` reproduces the reference's over-strict end-of-input check
 // (src/RawInflate.ts:187) and its exact `ip` bookkeeping.
-import native, { dflt } from './native.js';
+import native, { dflt, refError } from './native.js';
 import { BufferType, DefaultInflateBufferSize } from './Constants.js';
 
 export { BufferType };
@@ -12,6 +12,7 @@ export class RawInflate {
     constructor(input, opts = {}) {
         this.input = input instanceof Uint8Array ? input : new Uint8Array(input);
         this.ip = dflt(opts.index, 0);
+        this.streamStart = this.ip;  // where the stream starts (buildIndex: decompress() moves ip)
         this.bufferSize = dflt(opts.bufferSize, DefaultInflateBufferSize);
         this.bufferType = dflt(opts.bufferType, BufferType.ADAPTIVE);
         this.resize = dflt(opts.resize, false);
@@ -42,5 +43,39 @@ export class RawInflate {
         this.op = r.output.length;
         this.buffer = r.output;
         return r.output;
+    }
+
+    // Indexed random access (include/zt_index.h; this build's extension: the
+    // reference has none).  buildIndex() decodes the stream once and returns
+    // its index blob (a Uint8Array that may be stored); decompressRange /
+    // decompressRanges then decode only what the ranges need.  All three start
+    // at the constructor's `index` option and leave ip / output untouched.
+    // A stream without sync points throws 'stream has no usable sync points'
+    // (ztStatus -60); decode it with decompress().
+    buildIndex() {
+        try {
+            return native.inflateIndexBuild(this.input, this.streamStart);
+        } catch (e) {
+            throw refError(e);
+        }
+    }
+
+    decompressRange(indexBlob, offset, length) {
+        return this.decompressRanges(indexBlob, [[offset, length]])[0];
+    }
+
+    // ranges: [[offset, length], ...] (pread semantics: a length is clamped to
+    // the end of the output, an offset past it throws) -> Uint8Array[]
+    decompressRanges(indexBlob, ranges) {
+        const off = new Float64Array(ranges.length), len = new Float64Array(ranges.length);
+        for (let i = 0; i < ranges.length; i++) {
+            off[i] = ranges[i][0];
+            len[i] = ranges[i][1];
+        }
+        try {
+            return native.inflateRanges(this.input, indexBlob, off, len);
+        } catch (e) {
+            throw refError(e);
+        }
     }
 }

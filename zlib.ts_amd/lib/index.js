@@ -12,5 +12,6 @@ export { Inflate } from './Inflate.js';
 export { Zip, ZipCompressionMethod, ZipOperatingSystem, ZipFlags } from './Zip.js';
 export { Unzip } from './Unzip.js';
 import native from './native.js';
+export { ZT } from './native.js';
 export const deviceCount = () => native.deviceCount();
 export const version = () => native.version();

@@ -14,10 +14,13 @@ try {
 }
 export default addon;
 
-// libzt status codes (include/zt.h)
+// libzt status codes (include/zt.h, include/zt_index.h)
 export const ZT = {
     INVALID_COMPRESSION_TYPE: -1,
     INPUT_BROKEN: -10,
+    NO_INDEX: -60,
+    INDEX: -61,
+    INDEX_MISMATCH: -62,
 };
 
 // `a ?? b` (Node 12 has no nullish coalescing)

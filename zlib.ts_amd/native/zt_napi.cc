@@ -15,6 +15,7 @@
 #include "../../include/zt_zipcrypto.h"
 #include "../../include/zt_dict.h"
 #include "../../include/zt_container_batch.h"
+#include "../../include/zt_index.h"
 
 namespace {
 
@@ -630,6 +631,72 @@ napi_value unzip(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// ---- indexed random access (include/zt_index.h) ----------------------------------
+// inflateIndexBuild(input: Uint8Array, index) -> Uint8Array (the index blob)
+napi_value inflate_index_build(napi_env env, napi_callback_info info) {
+  napi_value a[2];
+  args(env, info, a, 2);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  const int64_t index = get_i64(env, a[1], 0);
+  uint8_t *idx = nullptr;
+  size_t ilen = 0;
+  const int rc = zt_inflate_index_build(p, n, index < 0 ? 0 : (size_t)index, &idx, &ilen, nullptr, nullptr, nullptr);
+  if (rc) return throw_zt(env, rc);
+  return new_u8(env, idx, ilen);
+}
+
+// inflateRanges(input: Uint8Array, indexBlob: Uint8Array, offsets: Float64Array, lengths: Float64Array)
+//   -> Uint8Array[]; the first failing range throws
+napi_value inflate_ranges(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  args(env, info, a, 4);
+  const uint8_t *p, *ix;
+  size_t n, in;
+  if (!get_u8(env, a[0], &p, &n) || !get_u8(env, a[1], &ix, &in)) return nullptr;
+  std::vector<uint64_t> off, len;
+  for (int k = 0; k < 2; ++k) {
+    bool is_ta = false;
+    napi_is_typedarray(env, a[2 + k], &is_ta);
+    napi_typedarray_type t = napi_uint8_array;
+    size_t cnt = 0, boff = 0;
+    void *data = nullptr;
+    napi_value ab;
+    if (is_ta) napi_get_typedarray_info(env, a[2 + k], &t, &cnt, &data, &ab, &boff);
+    if (!is_ta || t != napi_float64_array) {
+      napi_throw_type_error(env, nullptr, "expected a Float64Array");
+      return nullptr;
+    }
+    std::vector<uint64_t> &dst = k ? len : off;
+    const double *d = static_cast<const double *>(data);
+    for (size_t i = 0; i < cnt; ++i) {
+      if (!(d[i] >= 0) || d[i] > 9007199254740992.0) {
+        napi_throw_range_error(env, nullptr, "offset and length must be non-negative integers");
+        return nullptr;
+      }
+      dst.push_back((uint64_t)d[i]);
+    }
+  }
+  if (off.size() != len.size()) {
+    napi_throw_range_error(env, nullptr, "one length per offset");
+    return nullptr;
+  }
+  const size_t count = off.size();
+  std::vector<uint8_t *> out(count, nullptr);
+  std::vector<size_t> olen(count, 0);
+  std::vector<int> st(count, 0);
+  const int rc = zt_inflate_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(), st.data());
+  if (rc) {
+    for (uint8_t *o : out) zt_free(o);
+    return throw_zt(env, rc);
+  }
+  napi_value arr;
+  napi_create_array_with_length(env, count, &arr);
+  for (size_t i = 0; i < count; ++i) napi_set_element(env, arr, (uint32_t)i, new_u8(env, out[i], olen[i]));
+  return arr;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   napi_value r;
   napi_create_int32(env, zt_device_count(), &r);
@@ -657,6 +724,8 @@ napi_value init(napi_env env, napi_value exports) {
       {"zlibDecompressBatch", nullptr, zlib_decompress_batch, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"zipCompress", nullptr, zip_compress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"unzip", nullptr, unzip, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"inflateIndexBuild", nullptr, inflate_index_build, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"inflateRanges", nullptr, inflate_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
   };

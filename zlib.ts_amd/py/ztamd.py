@@ -17,7 +17,8 @@ ERRORS = {
     -15: "ZT_E_INVALID_DISTANCE", -16: "ZT_E_INVALID_SYMBOL", -17: "ZT_E_BAD_TREE",
     -30: "ZT_E_GZIP_SIGNATURE", -31: "ZT_E_GZIP_METHOD", -32: "ZT_E_GZIP_HCRC", -33: "ZT_E_GZIP_CRC32",
     -34: "ZT_E_GZIP_ISIZE", -40: "ZT_E_ZLIB_METHOD", -41: "ZT_E_ZLIB_FCHECK", -42: "ZT_E_ZLIB_FDICT",
-    -43: "ZT_E_ZLIB_ADLER", -44: "ZT_E_ZLIB_DICTID", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED", -100: "ZT_E_NO_DEVICE",
+    -43: "ZT_E_ZLIB_ADLER", -44: "ZT_E_ZLIB_DICTID", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED",
+    -60: "ZT_E_NO_INDEX", -61: "ZT_E_INDEX", -62: "ZT_E_INDEX_MISMATCH", -100: "ZT_E_NO_DEVICE",
     -101: "ZT_E_HIP", -102: "ZT_E_NOMEM", -103: "ZT_E_ARG", -104: "ZT_E_INTERNAL",
 }
 
@@ -83,6 +84,11 @@ class GzipMember(ctypes.Structure):
 
 class GunzipBatchStats(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in ("items", "candidates", "members", "decode_passes", "redecoded")]
+
+
+class IndexStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("builds", "range_calls", "ranges", "units_tokenized",
+                                               "in_bytes_uploaded", "out_bytes_decoded", "out_bytes_returned")]
 
 
 def _load():
@@ -173,6 +179,12 @@ def _load():
                                            P(ctypes.c_int)], ctypes.c_int),
         "zt_container_batch_message": ([sz], ctypes.c_char_p),
         "zt_gunzip_batch_last_stats": ([P(GunzipBatchStats)], ctypes.c_int),
+        # include/zt_index.h
+        "zt_inflate_index_build": ([vp, sz, sz, u8pp, P(sz), u8pp, P(sz), P(sz)], ctypes.c_int),
+        "zt_inflate_range": ([vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint64, u8pp, P(sz)], ctypes.c_int),
+        "zt_inflate_ranges": ([vp, sz, vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
+                               P(ctypes.c_int)], ctypes.c_int),
+        "zt_index_stats_read": ([P(IndexStats), ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -215,6 +227,12 @@ DICT_SYMBOLS = [
 CONTAINER_BATCH_SYMBOLS = [
     "zt_gunzip_batch", "zt_zlib_decompress_batch", "zt_zlib_decompress_batch_dict", "zt_container_batch_message",
     "zt_gunzip_batch_last_stats",
+]
+
+
+# every symbol include/zt_index.h declares (checked by tests/test_index_host.py)
+INDEX_SYMBOLS = [
+    "zt_inflate_index_build", "zt_inflate_range", "zt_inflate_ranges", "zt_index_stats_read",
 ]
 
 
@@ -681,6 +699,90 @@ def zlib_decompress(data, index=0, verify=False, dictionary=None):
         _check(lib.zt_zlib_decompress(b, n, index, int(verify), ctypes.byref(out), ctypes.byref(olen),
                                       ctypes.byref(ip), ctypes.byref(adler)))
     return _take(out, olen), ip.value
+
+
+# ---- indexed random access (include/zt_index.h) ------------------------------------
+def inflate_index_build(stream, index=0, want_output=False):
+    """zt_inflate_index_build: decodes the raw stream at stream[index:] once
+    and returns its index blob (bytes); want_output: (blob, output, end ip)."""
+    b, n = _cbuf(stream)
+    idx = ctypes.POINTER(ctypes.c_uint8)()
+    ilen = ctypes.c_size_t()
+    olen = ctypes.c_size_t()
+    ip = ctypes.c_size_t()
+    if want_output:
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        _check(lib.zt_inflate_index_build(b, n, index, ctypes.byref(idx), ctypes.byref(ilen), ctypes.byref(out),
+                                          ctypes.byref(olen), ctypes.byref(ip)))
+        return _take(idx, ilen), _take(out, olen), ip.value
+    _check(lib.zt_inflate_index_build(b, n, index, ctypes.byref(idx), ctypes.byref(ilen), None, ctypes.byref(olen),
+                                      ctypes.byref(ip)))
+    return _take(idx, ilen)
+
+
+def inflate_range(stream, idx, off, length):
+    """zt_inflate_range: bytes [off, off + length) of the stream's output (pread
+    semantics: length is clamped, off past the end raises ZT_E_ARG)."""
+    b, n = _cbuf(stream)
+    ib, il = _cbuf(idx)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    olen = ctypes.c_size_t()
+    _check(lib.zt_inflate_range(b, n, ib, il, off, length, ctypes.byref(out), ctypes.byref(olen)))
+    return _take(out, olen)
+
+
+def inflate_ranges(stream, idx, ranges, return_code=False):
+    """zt_inflate_ranges: [(off, len), ...] in one call.  Returns a list of
+    (status, bytes) pairs (bytes None for a failed range); return_code: also
+    the call's return code, as (code, list).  A call that fails before any
+    range is looked at (a bad index) raises."""
+    b, n = _cbuf(stream)
+    ib, il = _cbuf(idx)
+    k = len(ranges)
+    offs = (ctypes.c_uint64 * k)(*[r[0] for r in ranges])
+    lens = (ctypes.c_uint64 * k)(*[r[1] for r in ranges])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_inflate_ranges(b, n, ib, il, offs, lens, k, outs, olens, st)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    res = []
+    for i in range(k):
+        res.append((st[i], ctypes.string_at(outs[i], olens[i]) if st[i] == 0 else None))
+        if outs[i]:
+            lib.zt_free(outs[i])
+    return (rc, res) if return_code else res
+
+
+def index_stats(reset=False):
+    """Work counters of the index calls (zt_index_stats_read)."""
+    s = IndexStats()
+    _check(lib.zt_index_stats_read(ctypes.byref(s), 1 if reset else 0))
+    return {f: int(getattr(s, f)) for f, _ in IndexStats._fields_}
+
+
+INDEX_HEADER_BYTES = 64
+INDEX_ENTRY_BYTES = 24
+
+
+def index_entries(idx):
+    """An index blob parsed with numpy: (header dict, entries) -- entries a
+    record array (in_off, out_off, ntok, flags) of nunits + 1 rows, the
+    sentinel last.  Raises ValueError on a blob that is not an index."""
+    import numpy as np
+
+    idx = bytes(idx)
+    if len(idx) < INDEX_HEADER_BYTES or idx[:4] != b"ZTIX":
+        raise ValueError("not an index blob")
+    version, nunits, nseg = (int(x) for x in np.frombuffer(idx, dtype="<u4", count=3, offset=4))
+    start, end_ip, total = (int(x) for x in np.frombuffer(idx, dtype="<u8", count=3, offset=16))
+    if version != 1 or len(idx) != INDEX_HEADER_BYTES + (nunits + 1) * INDEX_ENTRY_BYTES:
+        raise ValueError("index blob version or length is wrong")
+    ent_t = np.dtype([("in_off", "<u8"), ("out_off", "<u8"), ("ntok", "<u4"), ("flags", "<u4")])
+    ent = np.frombuffer(idx, dtype=ent_t, count=nunits + 1, offset=INDEX_HEADER_BYTES)
+    return {"version": version, "nunits": nunits, "nseg": nseg, "stream_start": start, "end_ip": end_ip,
+            "total_out": total}, ent
 
 
 class BatchStatus(int):
