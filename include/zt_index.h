@@ -13,6 +13,12 @@
  * thread's device (zt_set_devices does not apply).  A gzip or zlib caller
  * passes the header length as `index`.
  *
+ * A stream this engine writes needs no second decode: the _indexed forms of
+ * the raw, gzip and zlib writers (below) return the index with the stream.
+ * The compressor knows its own unit boundaries, so this also covers inputs
+ * of any size the writer takes and stored data that happens to contain the
+ * sync bytes, where the build gives ZT_E_NO_INDEX.
+ *
  * The index is a hint that is verified, never trusted: the blob is checked on
  * the host before any device work, and every decoded unit is checked against
  * its neighbouring entries on the device.  A stale or forged index gives an
@@ -33,8 +39,10 @@
  *   the last entry is a sentinel: in_off = end_ip, out_off = total_out, ntok = flags = 0
  *
  * Not covered: streams without sync points (ZT_E_NO_INDEX; decode them with
- * zt_inflate_raw), streams too large for the one-call device decode, device
- * resident and multi-GPU forms, container-level helpers.
+ * zt_inflate_raw), an index *build* of streams too large for the one-call
+ * device decode (the _indexed writers have no such limit), device resident
+ * and multi-GPU forms, the batch and zip writers, container parsing on the
+ * read side (the _indexed gzip and zlib writers set stream_start themselves).
  */
 #ifndef ZT_INDEX_H
 #define ZT_INDEX_H
@@ -88,6 +96,36 @@ typedef struct {
   uint64_t out_bytes_returned;/* bytes the range calls returned */
 } zt_index_stats;
 int zt_index_stats_read(zt_index_stats *out, int reset);
+
+/* ---- the write side: the index of a stream as it is written --------------------
+ * zt_deflate_raw / zt_gzip_compress / zt_zlib_compress with the index of
+ * their output: *out is byte for byte what the plain call returns for the
+ * same arguments, *idx (free with zt_free) a version-1 blob, byte-identical to
+ * what zt_inflate_index_build returns for that output wherever that build
+ * succeeds.  No second decode: one small kernel behind the encoder writes the
+ * entries from what the deflate pipeline already holds.
+ *
+ * Raw: `stream_start` is where the caller will place the stream in the buffer
+ * later handed to zt_inflate_range (a prefix of their own); it is the
+ * header's stream_start and is added to every in_off and to end_ip.  gzip:
+ * stream_start is the written header's length; zlib: 2 -- the container file
+ * and its index go straight into zt_inflate_range.
+ *
+ * compression_type NONE (or level 0) writes stored blocks without sync points,
+ * and the empty input one empty stored block: ZT_E_NO_INDEX as from the build,
+ * before any device work, and no output.  (Preset dictionaries
+ * have no indexed form: the range path has none.)
+ *
+ * ZT_INDEX_WRITER marks the write side's declarations, apart from the four
+ * read-side calls above. */
+#define ZT_INDEX_WRITER
+ZT_INDEX_WRITER int zt_deflate_raw_indexed(const uint8_t *in, size_t n, const zt_deflate_opts *opts,
+                                           size_t stream_start, uint8_t **out, size_t *out_len, uint8_t **idx,
+                                           size_t *idx_len);
+ZT_INDEX_WRITER int zt_gzip_compress_indexed(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out,
+                                             size_t *out_len, uint32_t *crc_out, uint8_t **idx, size_t *idx_len);
+ZT_INDEX_WRITER int zt_zlib_compress_indexed(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out,
+                                             size_t *out_len, uint32_t *adler_out, uint8_t **idx, size_t *idx_len);
 
 #ifdef __cplusplus
 }

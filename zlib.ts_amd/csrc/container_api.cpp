@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/zt_index.h"
 #include "gunzip_chain.h"
 #include "zt_internal.h"
 
@@ -21,15 +22,27 @@ namespace {
 
 // Raw DEFLATE of host bytes into `out` after `prefix` bytes of header, with the
 // input's CRC-32 and/or Adler-32 from the same device copy of the input.
-// *out (malloc'd) = prefix | stream | `trailer` bytes of room.
+// *out (malloc'd) = prefix | stream | `trailer` bytes of room.  With idx
+// non-null (the _indexed calls) the stream's deflate-time index comes back
+// too, its positions counted in *out: stream_start = prefix_len.
 int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *opts, const uint8_t *prefix,
                            size_t prefix_len, size_t trailer, uint8_t **out, size_t *stream_len, uint32_t *crc,
-                           uint32_t *adler) {
+                           uint32_t *adler, uint8_t **idx = nullptr, size_t *idx_len = nullptr) {
+  int ct, lv;
+  if (idx) {  // (before any device work)
+    ZT_TRY(resolve_opts(opts, &ct, &lv));
+    ZT_TRY(deflate_index_refuse(ct, n));
+  }
   DeviceCtx *c;
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-  int ct, lv;
   ZT_TRY(resolve_opts(opts, &ct, &lv));
+  DeflateIndexTable tab;
+  DeflateIndexReq req{};
+  if (idx) {
+    ZT_TRY(deflate_index_begin(c, std::vector<size_t>{n}, prefix_len, &tab));
+    req = deflate_index_piece(tab, 0, 0, 0);
+  }
   const size_t ob = deflate_out_bound(ct, n);
   void *d_in, *d_out, *d_scr, *d_res;
   ZT_TRY(scratch(c, kIn, n + 64, &d_in));
@@ -50,17 +63,24 @@ int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *o
     ZT_HIP(hipMemcpyAsync(sums, d_res, sizeof sums, hipMemcpyDeviceToHost, c->aux));
   }
   size_t len = 0;
-  ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in, n, 0, 1, ct, lv, (uint8_t *)d_out, &len, d_scr, ss, c->stream));
+  ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in, n, 0, 1, ct, lv, (uint8_t *)d_out, &len, d_scr, ss, c->stream,
+                         idx ? &req : nullptr));
   uint8_t *h = host_out(prefix_len + len + trailer + 1);
   if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
   if (prefix_len) memcpy(h, prefix, prefix_len);
-  if (const int rc = download(c, h + prefix_len, d_out, len, c->stream)) {
+  int drc = download(c, h + prefix_len, d_out, len, c->stream);
+  if (!drc && idx) drc = deflate_index_finish(c, tab, len, n, idx, idx_len, c->stream);
+  if (drc) {
     zt_free(h);
-    return rc;
+    return drc;
   }
   hipError_t e = hipStreamSynchronize(c->aux);
   if (e != hipSuccess) {
     zt_free(h);
+    if (idx && *idx) {
+      zt_free(*idx);
+      *idx = nullptr;
+    }
     return hip_fail(e, "hipStreamSynchronize");
   }
   if (crc) *crc = sums[0];
@@ -111,8 +131,9 @@ using namespace zt;
 
 extern "C" {
 
-int zt_gzip_compress(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out, size_t *out_len,
-                     uint32_t *crc_out) {
+// zt_gzip_compress, and with idx non-null zt_gzip_compress_indexed
+static int gzip_compress_host(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out, size_t *out_len,
+                              uint32_t *crc_out, uint8_t **idx, size_t *idx_len) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
   std::vector<uint8_t> hd;
@@ -121,7 +142,7 @@ int zt_gzip_compress(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint
   size_t slen;
   uint32_t crc;
   ZT_TRY(deflate_with_checksums(in, n, opts ? &opts->deflate : nullptr, hd.data(), hd.size(), 8, &buf, &slen, &crc,
-                                nullptr));
+                                nullptr, idx, idx_len));
   // trailer: CRC-32 and ISIZE (src/GZip.ts:179-185)
   put32le(buf + hd.size() + slen, crc);
   put32le(buf + hd.size() + slen + 4, (uint32_t)n);
@@ -129,6 +150,20 @@ int zt_gzip_compress(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint
   *out_len = hd.size() + slen + 8;
   if (crc_out) *crc_out = crc;
   return ZT_OK;
+}
+
+int zt_gzip_compress(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out, size_t *out_len,
+                     uint32_t *crc_out) {
+  return gzip_compress_host(in, n, opts, out, out_len, crc_out, nullptr, nullptr);
+}
+
+int zt_gzip_compress_indexed(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out, size_t *out_len,
+                             uint32_t *crc_out, uint8_t **idx, size_t *idx_len) {
+  if (!idx || !idx_len) return set_error(ZT_E_ARG, "null index output");
+  if (out) *out = nullptr;
+  *idx = nullptr;
+  *idx_len = 0;
+  return gzip_compress_host(in, n, opts, out, out_len, crc_out, idx, idx_len);
 }
 
 int zt_gunzip(const uint8_t *in, size_t n, uint8_t **out, size_t *out_len, zt_gzip_member **members,
@@ -193,8 +228,9 @@ int zt_gunzip(const uint8_t *in, size_t n, uint8_t **out, size_t *out_len, zt_gz
   return ZT_OK;
 }
 
-int zt_zlib_compress(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len,
-                     uint32_t *adler_out) {
+// zt_zlib_compress, and with idx non-null zt_zlib_compress_indexed
+static int zlib_compress_host(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out,
+                              size_t *out_len, uint32_t *adler_out, uint8_t **idx, size_t *idx_len) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
   const int ct = opts ? opts->compression_type : 2;
@@ -205,7 +241,7 @@ int zt_zlib_compress(const uint8_t *in, size_t n, const zt_deflate_opts *opts, u
   uint8_t *buf;
   size_t slen;
   uint32_t adler;
-  ZT_TRY(deflate_with_checksums(in, n, opts, hd, 2, 4, &buf, &slen, nullptr, &adler));
+  ZT_TRY(deflate_with_checksums(in, n, opts, hd, 2, 4, &buf, &slen, nullptr, &adler, idx, idx_len));
   // Adler-32, big-endian (src/Deflate.ts:95)
   uint8_t *t = buf + 2 + slen;
   t[0] = adler >> 24;
@@ -216,6 +252,20 @@ int zt_zlib_compress(const uint8_t *in, size_t n, const zt_deflate_opts *opts, u
   *out_len = 2 + slen + 4;
   if (adler_out) *adler_out = adler;
   return ZT_OK;
+}
+
+int zt_zlib_compress(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len,
+                     uint32_t *adler_out) {
+  return zlib_compress_host(in, n, opts, out, out_len, adler_out, nullptr, nullptr);
+}
+
+int zt_zlib_compress_indexed(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len,
+                             uint32_t *adler_out, uint8_t **idx, size_t *idx_len) {
+  if (!idx || !idx_len) return set_error(ZT_E_ARG, "null index output");
+  if (out) *out = nullptr;
+  *idx = nullptr;
+  *idx_len = 0;
+  return zlib_compress_host(in, n, opts, out, out_len, adler_out, idx, idx_len);
 }
 
 int zt_zlib_decompress(const uint8_t *in, size_t n, size_t index, int verify, uint8_t **out, size_t *out_len,

@@ -1696,10 +1696,11 @@ static DeflateParams deflate_params(int level, int ctype, uint32_t nblocks, cons
 }
 
 // The pipeline on s: classify -> match (nwg workgroups; D: the _dict kernels)
-// -> deflate_post_run, then off[first .. nblocks] read back into h_off and
-// the fault check.
+// -> deflate_post_run (-> deflate_index_kernel when the call asks for its
+// index entries), then off[first .. nblocks] read back into h_off and the
+// fault check.
 static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off, uint32_t nwg, const DictView *D,
-                            uint32_t first, uint64_t *h_off, hipStream_t s) {
+                            uint32_t first, uint64_t *h_off, hipStream_t s, const DeflateIndexReq *ix = nullptr) {
   ZT_TRY(timing_begin(c, s, 1));
   ZT_HIP(hipMemsetAsync(P.nstore, 0, 8, s));
   if (P.store) {
@@ -1718,7 +1719,8 @@ static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off,
   ZT_TRY(timing_end(c, s, 0));
   ZT_TRY(deflate_post_run(P, off, s));
   ZT_TRY(timing_end(c, s, 1));
-  uint32_t nst[2] = {0, 0};  // blocks stored unsearched, encode faults
+  if (ix) ZT_TRY(deflate_index_launch(P, *ix, s));
+  uint32_t nst[2] = {0, 0};  // blocks stored unsearched, fault bits
   {
     void *mb;
     const size_t bb = (size_t)(P.nblocks + 1 - first) * 8;
@@ -1729,7 +1731,8 @@ static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off,
     memcpy(h_off, mb, bb);
     memcpy(nst, (uint8_t *)mb + bb, 8);
   }
-  if (nst[1]) return set_error(ZT_E_INTERNAL, "deflate: a block's encoded size differs from its plan");
+  if (nst[1] & kFaultEncode) return set_error(ZT_E_INTERNAL, "deflate: a block's encoded size differs from its plan");
+  if (nst[1]) return set_error(ZT_E_INTERNAL, "deflate: the index entries do not follow the restart markers");
   c->times.blocks_unsearched += nst[0];
   ZT_TRY(timing_collect(c, &c->times.deflate_ms, &c->times.deflate_launches, 0));
   ZT_TRY(timing_collect(c, &c->times.deflate_pipeline_ms, &c->times.deflate_pipelines, 1));
@@ -1737,7 +1740,9 @@ static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off,
 }
 
 int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype, int level,
-                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s) {
+                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s,
+                    const DeflateIndexReq *ix) {
+  if (ix && (n == 0 || ctype == 0)) return set_error(ZT_E_INTERNAL, "deflate: no index entries for this call");
   if (n == 0) {  // one empty stored block
     write_bytes<<<1, 64, 0, s>>>(d_out, final_ ? 0xFFFF000001ull : 0xFFFF000000ull, 5);
     ZT_HIP(hipGetLastError());
@@ -1766,7 +1771,7 @@ int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, in
   P.tail_k = G.tail_k;
   P.restart = (kRestartBlocks + G.k - 1) / G.k * G.k;
   uint64_t total = 0;
-  ZT_TRY(deflate_pipeline(c, P, S.off, G.nwg, nullptr, nblocks, &total, s));
+  ZT_TRY(deflate_pipeline(c, P, S.off, G.nwg, nullptr, nblocks, &total, s, ix));
   *out_len = total;
   return ZT_OK;
 }

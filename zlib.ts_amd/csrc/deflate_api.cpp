@@ -5,9 +5,53 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/zt_index.h"
 #include "zt_internal.h"
 
 using namespace zt;
+
+// ---- the deflate-time index's host side (zt_internal.h) ---------------------------
+namespace zt {
+
+int deflate_index_begin(DeviceCtx *c, const std::vector<size_t> &sizes, uint64_t stream_start, DeflateIndexTable *t) {
+  t->L = dix_layout(sizes, kRestartBlocks);
+  t->stream_start = stream_start;
+  if (t->L.nunits >= 0x7FFFFFFFull) return set_error(ZT_E_ARG, "input too large for one index");
+  void *p;
+  ZT_TRY(scratch(c, kDeflateIndex, (size_t)(t->L.nunits + 1) * sizeof(IdxEntry), &p));
+  t->d_ent = static_cast<IdxEntry *>(p);
+  return ZT_OK;
+}
+
+DeflateIndexReq deflate_index_piece(const DeflateIndexTable &t, size_t i, uint64_t stream_pos, uint64_t input_pos) {
+  const bool last = i + 2 == t.L.first.size();
+  return DeflateIndexReq{t.d_ent + t.L.first[i], t.L.first[i + 1] - t.L.first[i] + (last ? 1 : 0),
+                         t.stream_start + stream_pos, input_pos};
+}
+
+int deflate_index_finish(DeviceCtx *c, const DeflateIndexTable &t, uint64_t stream_len, uint64_t total_out,
+                         uint8_t **idx, size_t *idx_len, hipStream_t s) {
+  const size_t bytes = index_blob_bytes((size_t)t.L.nunits);
+  uint8_t *blob = host_out(bytes);
+  if (!blob) return set_error(ZT_E_NOMEM, "host allocation failed");
+  int rc = download(c, blob + kIdxHeader, t.d_ent, (size_t)(t.L.nunits + 1) * sizeof(IdxEntry), s);
+  if (!rc)
+    if (const char *why = dix_finish(blob, (size_t)t.L.nunits, t.stream_start, stream_len, total_out))
+      rc = set_error(ZT_E_INTERNAL, std::string("deflate index: ") + why);
+  if (rc) {
+    zt_free(blob);
+    return rc;
+  }
+  *idx = blob;
+  *idx_len = bytes;
+  return ZT_OK;
+}
+
+int deflate_index_refuse(int ctype, size_t n) {
+  return ctype == 0 || n == 0 ? set_error(ZT_E_NO_INDEX, "stream has no usable sync points") : ZT_OK;
+}
+
+}  // namespace zt
 
 struct zt_deflate_plan {
   int device;
@@ -120,9 +164,18 @@ static std::vector<size_t> deflate_pieces(size_t n, size_t seg) {
   return sizes;
 }
 
+// With `ix` (zt_deflate_raw_indexed): each piece's deflate_index_kernel writes
+// its entries into the one table, at an entry offset known from the piece
+// sizes, with the stream bytes written so far as its input base -- known on
+// the host when the previous piece's deflate_dev_run has returned; the table
+// comes back once, after the last piece.
 static int deflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, int ct, int lv, uint8_t **out,
-                                 size_t *out_len) {
+                                 size_t *out_len, uint64_t stream_start = 0, uint8_t **idx = nullptr,
+                                 size_t *idx_len = nullptr) {
   const std::vector<size_t> sizes = deflate_pieces(n, deflate_segment_bytes());
+  DeflateIndexTable tab;
+  if (idx) ZT_TRY(deflate_index_begin(c, sizes, stream_start, &tab));
+  uint64_t written = 0;  // stream bytes of the pieces computed so far
   const size_t np = sizes.size();
   std::vector<size_t> in_off(np + 1, 0), out_off(np + 1, 0);
   size_t pmax = 0;
@@ -145,8 +198,11 @@ static int deflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, int 
       [&](size_t i) { return PipePiece{in + in_off[i], (uint8_t *)d_in + in_off[i], sizes[i]}; },
       [&](size_t i, const void **d_res, size_t *n_res) -> int {
         uint8_t *d_o = (uint8_t *)d_out + out_off[i];
+        DeflateIndexReq req{};
+        if (idx) req = deflate_index_piece(tab, i, written, in_off[i]);
         ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in + in_off[i], sizes[i], 0, i + 1 == np, ct, lv, d_o, n_res,
-                               d_scr, ss, c->stream));
+                               d_scr, ss, c->stream, idx ? &req : nullptr));
+        written += *n_res;
         *d_res = d_o;
         return ZT_OK;
       },
@@ -155,13 +211,22 @@ static int deflate_raw_pipelined(DeviceCtx *c, const uint8_t *in, size_t n, int 
     host_discard(po.base);
     return rc;
   }
+  if (idx) {
+    if (const int irc = deflate_index_finish(c, tab, po.total, n, idx, idx_len, c->stream)) {
+      host_discard(po.base);
+      return irc;
+    }
+  }
   host_out_used(po.base, po.total);  // (zt_free registers the stream's pages, not the bound's)
   *out = po.base;
   *out_len = po.total;
   return ZT_OK;
 }
 
-int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len) {
+// zt_deflate_raw, and with idx non-null zt_deflate_raw_indexed: the same
+// stream, and the index of it placed at `stream_start`
+static int deflate_raw_host(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint64_t stream_start,
+                            uint8_t **out, size_t *out_len, uint8_t **idx, size_t *idx_len) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
   DeviceCtx *c;
@@ -169,7 +234,13 @@ int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uin
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   int ct, lv;
   ZT_TRY(resolve_opts(opts, &ct, &lv));
-  if (ct != 0 && n >= kPipeMin) return deflate_raw_pipelined(c, in, n, ct, lv, out, out_len);
+  if (ct != 0 && n >= kPipeMin) return deflate_raw_pipelined(c, in, n, ct, lv, out, out_len, stream_start, idx, idx_len);
+  DeflateIndexTable tab;
+  DeflateIndexReq req{};
+  if (idx) {
+    ZT_TRY(deflate_index_begin(c, std::vector<size_t>{n}, stream_start, &tab));
+    req = deflate_index_piece(tab, 0, 0, 0);
+  }
   const size_t ob = deflate_out_bound(ct, n);
   void *d_in, *d_out, *d_scr;
   ZT_TRY(scratch(c, kIn, n + 64, &d_in));
@@ -178,10 +249,12 @@ int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uin
   ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
   ZT_TRY(upload(c, d_in, in, n, c->stream));
   size_t len = 0;
-  ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in, n, 0, 1, ct, lv, (uint8_t *)d_out, &len, d_scr, ss, c->stream));
+  ZT_TRY(deflate_dev_run(c, (const uint8_t *)d_in, n, 0, 1, ct, lv, (uint8_t *)d_out, &len, d_scr, ss, c->stream,
+                         idx ? &req : nullptr));
   uint8_t *h = host_out(len, true);
   if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
-  const int rc = download(c, h, d_out, len, c->stream);
+  int rc = download(c, h, d_out, len, c->stream);
+  if (!rc && idx) rc = deflate_index_finish(c, tab, len, n, idx, idx_len, c->stream);
   if (rc) {
     zt_free(h);
     return rc;
@@ -189,6 +262,22 @@ int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uin
   *out = h;
   *out_len = len;
   return ZT_OK;
+}
+
+int zt_deflate_raw(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len) {
+  return deflate_raw_host(in, n, opts, 0, out, out_len, nullptr, nullptr);
+}
+
+int zt_deflate_raw_indexed(const uint8_t *in, size_t n, const zt_deflate_opts *opts, size_t stream_start,
+                           uint8_t **out, size_t *out_len, uint8_t **idx, size_t *idx_len) {
+  if (!idx || !idx_len) return set_error(ZT_E_ARG, "null index output");
+  if (out) *out = nullptr;
+  *idx = nullptr;
+  *idx_len = 0;
+  int ct, lv;
+  ZT_TRY(resolve_opts(opts, &ct, &lv));
+  ZT_TRY(deflate_index_refuse(ct, n));  // (before any device work)
+  return deflate_raw_host(in, n, opts, stream_start, out, out_len, idx, idx_len);
 }
 
 int zt_inflate_plan_create(size_t max_in, size_t max_out, zt_inflate_plan **plan) {

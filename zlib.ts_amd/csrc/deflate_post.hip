@@ -27,6 +27,7 @@
 //
 // Shared with deflate.hip through zt_internal.h ("deflate device pipeline"):
 // DeflateParams, BlockPlan, the res word format and the block geometry.
+#include "deflate_index_host.h"
 #include "zt_internal.h"
 
 namespace zt {
@@ -1445,9 +1446,6 @@ __device__ __forceinline__ void enc_copy(uint8_t *dst, const uint8_t *src, uint3
   for (uint32_t i = h + 4 * n4 + t; i < n; i += ENC_THREADS) dst[i] = src[i];
 }
 
-__device__ __forceinline__ bool restart_after(uint32_t b, uint32_t n, uint32_t restart, int final_,
-                                              const uint64_t *span);
-
 // one workgroup per DEFLATE block (launched per parse block; followers
 // return): the block goes straight to its place in the stream, out +
 // boff[blk] (its size was planned exactly by block_kernel and placed by
@@ -1635,15 +1633,8 @@ __global__ __launch_bounds__(ENC_THREADS) void encode_kernel(DeflateParams P) {
 // An ordinary block boundary carries at most one, so the 10-byte pattern at a
 // stored-block end marks a segment that inflate may decode on its own.
 // (a non-final call -- a shard -- also ends with the marker: the next shard
-// is independent when deflated with halo 0, see zt_shard.py)
-__device__ __forceinline__ bool restart_after(uint32_t b, uint32_t n, uint32_t restart, int final_,
-                                              const uint64_t *span) {
-  if (span) {  // batch: inside a stream only (its last block carries BFINAL)
-    const uint64_t nx = (uint64_t)(b + 1) * DF_BLOCK;
-    return nx < span[2 * (uint64_t)b + 1] && ((nx - span[2 * (uint64_t)b]) / DF_BLOCK) % restart == 0;
-  }
-  return (b + 1 < n) ? ((b + 1) % restart) == 0 : !final_;
-}
+// is independent when deflated with halo 0, see zt_shard.py).  The rule is
+// restart_after (deflate_index_host.h: the deflate-time index shares it).
 
 __global__ __launch_bounds__(1024) void scan_sizes(const uint32_t *__restrict__ len, uint32_t n,
                                                    uint64_t *__restrict__ off, uint64_t base, uint32_t restart,

@@ -13,6 +13,7 @@
 
 #include "../../include/zt.h"
 #include "batch_plan.h"
+#include "deflate_index_host.h"
 #include "dict_host.h"
 #include "inflate_chain.h"
 
@@ -79,7 +80,8 @@ enum ScratchSlot : int {
   kContainerIn = 19,  // unzip / gunzip member input (zip_api, container_api) and zt_gunzip_batch's member scan;
                     // the holder may call the inflate and checksum launchers (none asks for it)
   kSyncSort = 20,   // inflate_segments_dev: sort storage | keys | flags | positions | token offsets, up to the device chain
-  kStoredRuns = 21, // (unused)
+  kDeflateIndex = 21,  // deflate-time index (deflate_api.cpp, container_api.cpp): the entry table of the stream
+                    // being written; whole call (the deflate launchers never ask for it)
   kPipeOut = 22,    // pipelined host inflate's output; the holder calls inflate_parallel_dev (never asks for 22-25)
   kPipeRing0 = 23,  // 23-25: its overflow ring, piece i's buffer reused once piece i - 3 has left the device
   kGenJump = 26,    // general inflate's window pointer-jumping buffers
@@ -484,8 +486,45 @@ extern "C" int zt_debug_head_formats(uint64_t out[2]);
 size_t deflate_bound_bytes(size_t n);
 size_t deflate_segment_bytes();
 size_t deflate_scratch_bytes(const DeviceCtx *c, size_t n);
+// The deflate-time index of one deflate_dev_run call (include/zt_index.h; the
+// arithmetic: deflate_index_host.h): deflate_index_kernel, launched behind
+// encode_kernel, writes the call's dix_call_units entries (a final call: and
+// the sentinel) to d_ent; `cap` is that count exactly (dix_layout).  in_base: where the call's
+// first stream byte will lie in the caller's buffer; out_base: the output
+// offset of its first input byte.  n > 0 and a compressing ctype only.
+struct DeflateIndexReq {
+  IdxEntry *d_ent;
+  uint64_t cap;
+  uint64_t in_base, out_base;
+};
+int deflate_index_launch(const DeflateParams &P, const DeflateIndexReq &ix, hipStream_t s);  // deflate_index.hip
+// bits of DeflateParams::fault
+constexpr uint32_t kFaultEncode = 1;  // encode_kernel: a block's bits differ from its plan
+constexpr uint32_t kFaultIndex = 2;   // deflate_index_kernel: the entry layout disagrees with restart_after
 int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype, int level,
-                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s);
+                    uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s,
+                    const DeflateIndexReq *ix = nullptr);
+// The host side of a stream's deflate-time index (deflate_api.cpp), shared by
+// the raw and the container calls: the table of a stream written as pieces of
+// `sizes` input bytes (one piece: a one-call deflate) in scratch slot
+// kDeflateIndex; piece i's request for deflate_dev_run (stream_pos: the
+// stream bytes written before the piece; input_pos: its first input byte);
+// and, once the stream is complete, the table's one download into a blob
+// (zt_free) with its header, checked by index_validate.
+struct DeflateIndexTable {
+  DixLayout L;
+  IdxEntry *d_ent = nullptr;
+  uint64_t stream_start = 0;
+};
+int deflate_index_begin(DeviceCtx *c, const std::vector<size_t> &sizes, uint64_t stream_start, DeflateIndexTable *t);
+DeflateIndexReq deflate_index_piece(const DeflateIndexTable &t, size_t i, uint64_t stream_pos, uint64_t input_pos);
+int deflate_index_finish(DeviceCtx *c, const DeflateIndexTable &t, uint64_t stream_len, uint64_t total_out,
+                         uint8_t **idx, size_t *idx_len, hipStream_t s);
+// The indexed calls' refusal, before any device work, of a stream without
+// sync points: stored blocks only (NONE, level 0), or the empty input's one
+// empty stored block -- zt_inflate_index_build finds no sync point in that
+// stream either, and the writers answer as it does.  ZT_OK: indexable.
+int deflate_index_refuse(int ctype, size_t n);
 // batch deflate (deflate.hip): streams packed at 32 KiB boundaries, one pipeline
 size_t deflate_batch_scratch_bytes(const DeviceCtx *c, size_t padded);
 // a preset dictionary as the match kernel reads it (dict_host.h: dict_layout):

@@ -16,6 +16,12 @@ export class Deflate {
         this.dictionary = opts.dictionary == null ? undefined
             : opts.dictionary instanceof Uint8Array ? opts.dictionary : new Uint8Array(opts.dictionary);
         this.adler32 = undefined;
+        // this build's extra option: buildIndex: true leaves the stream's range
+        // index (include/zt_index.h) in streamIndex after compress(); the stream
+        // and the blob go straight into RawInflate.decompressRange.  Not with a
+        // preset dictionary: the range path has none.
+        this.buildIndex = dflt(opts.buildIndex, false);
+        this.streamIndex = undefined;
     }
 
     static compress(input, opts) {
@@ -25,7 +31,17 @@ export class Deflate {
     compress() {
         let r;
         try {
-            r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level, this.dictionary);
+            if (this.buildIndex) {
+                if (this.dictionary !== undefined) {
+                    const err = new Error('an indexed stream cannot use a preset dictionary');
+                    err.ztStatus = -103;
+                    throw err;
+                }
+                r = native.zlibCompressIndexed(this.input, this.compressionType, this.lazy, this.level);
+                this.streamIndex = r.index;
+            } else {
+                r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level, this.dictionary);
+            }
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';
             throw refError(e);

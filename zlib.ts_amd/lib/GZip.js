@@ -46,6 +46,11 @@ export class GZip {
         this.deflateOptions = dflt(opts.deflateOptions, {});
         // engine extension: a fixed MTIME (the reference always writes the current time)
         this.mtime = opts.mtime;
+        // engine extension: buildIndex: true leaves the member's range index
+        // (include/zt_index.h) in streamIndex after compress(); the member and
+        // the blob go straight into RawInflate.decompressRange
+        this.buildIndex = dflt(opts.buildIndex, false);
+        this.streamIndex = undefined;
     }
 
     compress() {
@@ -55,7 +60,7 @@ export class GZip {
         const mtime = dflt(this.mtime, Math.floor(Date.now() / 1000));
         let r;
         try {
-            r = native.gzipCompress(d, ct, dflt(o.lazy, 0), dflt(o.level, 6),
+            r = (this.buildIndex ? native.gzipCompressIndexed : native.gzipCompress)(d, ct, dflt(o.lazy, 0), dflt(o.level, 6),
                 this.flags.fname ? headerBytes(this.filename) : null,
                 this.flags.fcomment ? headerBytes(this.comment) : null, !!this.flags.fhcrc, mtime >>> 0);
         } catch (e) {
@@ -64,6 +69,7 @@ export class GZip {
         }
         this.crc32 = r.crc32;
         this.output = r.output;
+        if (this.buildIndex) this.streamIndex = r.index;
         this.op = r.output.length - 8;  // RawDeflate.op: end of the DEFLATE stream (src/GZip.ts:166)
         return r.output;
     }

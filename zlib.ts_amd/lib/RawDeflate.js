@@ -1,8 +1,12 @@
 // RawDeflate with the reference's surface (src/RawDeflate.ts:43-114): same
 // constructor options, public fields and return value; the compression runs in
 // libzt on the GPU (zt_deflate_raw).  `level` (1..9, default 6) is this
-// build's extra option; the reference has none.
-import native, { dflt } from './native.js';
+// build's extra option; the reference has none.  So is `buildIndex: true`:
+// compress() then also leaves the stream's range index (include/zt_index.h,
+// the blob RawInflate.decompressRange takes) in `streamIndex`, written with the
+// stream instead of by a second decode; its positions count from the start of
+// the returned buffer, so with `outputIndex` the caller's prefix is in front.
+import native, { dflt, refError } from './native.js';
 import { CompressionType, DefaultDeflateBufferSize } from './Constants.js';
 
 export { CompressionType };
@@ -23,6 +27,8 @@ export class RawDeflate {
             this.output = new Uint8Array(DefaultDeflateBufferSize);
         }
         this.op = dflt(opts.outputIndex, 0);
+        this.buildIndex = dflt(opts.buildIndex, false);
+        this.streamIndex = undefined;
     }
 
     // Returns bytes [0, op): any caller prefix in outputBuffer[0..outputIndex)
@@ -37,10 +43,21 @@ export class RawDeflate {
         }
         let stream;
         try {
-            stream = native.deflateRaw(this.input, ct, this.lazy, this.level, this.dictionary);
+            if (this.buildIndex) {
+                if (this.dictionary !== undefined) {
+                    const err = new Error('an indexed stream cannot use a preset dictionary');
+                    err.ztStatus = -103;
+                    throw err;
+                }
+                const r = native.deflateRawIndexed(this.input, ct, this.lazy, this.level, this.op);
+                stream = r.output;
+                this.streamIndex = r.index;
+            } else {
+                stream = native.deflateRaw(this.input, ct, this.lazy, this.level, this.dictionary);
+            }
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';
-            throw e;
+            throw this.buildIndex ? refError(e) : e;
         }
         const start = this.op;
         if (start === 0) {  // no caller prefix: the library's buffer itself (no copy)

@@ -256,7 +256,8 @@ bool opt_u8(napi_env env, napi_value v, const uint8_t **p, size_t *n, bool *pres
 }
 
 // gzipCompress(input, compressionType, lazy, level, name|null, comment|null, hcrc, mtime) -> {output, crc32}
-napi_value gzip_compress(napi_env env, napi_callback_info info) {
+// (indexed: gzipCompressIndexed, the same arguments -> {output, crc32, index})
+napi_value gzip_compress_any(napi_env env, napi_callback_info info, bool indexed) {
   napi_value a[8];
   args(env, info, a, 8);
   const uint8_t *p;
@@ -278,17 +279,21 @@ napi_value gzip_compress(napi_env env, napi_callback_info info) {
   if (t == napi_boolean) napi_get_value_bool(env, a[6], &hcrc);
   o.fhcrc = hcrc;
   o.mtime = get_u32(env, a[7], 0);
-  uint8_t *out = nullptr;
-  size_t olen = 0;
+  uint8_t *out = nullptr, *idx = nullptr;
+  size_t olen = 0, ilen = 0;
   uint32_t crc = 0;
-  int rc = zt_gzip_compress(p, n, &o, &out, &olen, &crc);
+  int rc = indexed ? zt_gzip_compress_indexed(p, n, &o, &out, &olen, &crc, &idx, &ilen)
+                   : zt_gzip_compress(p, n, &o, &out, &olen, &crc);
   if (rc) return throw_zt(env, rc);
   napi_value obj;
   napi_create_object(env, &obj);
   napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
   set_num(env, obj, "crc32", crc);
+  if (indexed) napi_set_named_property(env, obj, "index", new_u8(env, idx, ilen));
   return obj;
 }
+napi_value gzip_compress(napi_env env, napi_callback_info info) { return gzip_compress_any(env, info, false); }
+napi_value gzip_compress_indexed(napi_env env, napi_callback_info info) { return gzip_compress_any(env, info, true); }
 
 // [{flg, mtime, xfl, os, xlen, nameOff, nameLen, commentOff, commentLen, crc16 (or -1), crc32, isize,
 //   dataOff, dataLen}] of cnt members
@@ -631,6 +636,54 @@ napi_value unzip(napi_env env, napi_callback_info info) {
   return obj;
 }
 
+// ---- the deflate-time index (include/zt_index.h, the write side) ------------------
+// deflateRawIndexed(input, compressionType, lazy, level, streamStart) -> {output, index}
+napi_value deflate_raw_indexed(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  args(env, info, a, 5);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  zt_deflate_opts o;
+  o.compression_type = (int)get_i64(env, a[1], 2);
+  o.lazy = (int)get_i64(env, a[2], 0);
+  o.level = (int)get_i64(env, a[3], -1);
+  const int64_t start = get_i64(env, a[4], 0);
+  uint8_t *out = nullptr, *idx = nullptr;
+  size_t olen = 0, ilen = 0;
+  const int rc = zt_deflate_raw_indexed(p, n, &o, start < 0 ? 0 : (size_t)start, &out, &olen, &idx, &ilen);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj;
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
+  napi_set_named_property(env, obj, "index", new_u8(env, idx, ilen));
+  return obj;
+}
+
+// zlibCompressIndexed(input, compressionType, lazy, level) -> {output, adler32, index}
+napi_value zlib_compress_indexed(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  args(env, info, a, 4);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  zt_deflate_opts o;
+  o.compression_type = (int)get_i64(env, a[1], 2);
+  o.lazy = (int)get_i64(env, a[2], 0);
+  o.level = (int)get_i64(env, a[3], -1);
+  uint8_t *out = nullptr, *idx = nullptr;
+  size_t olen = 0, ilen = 0;
+  uint32_t adler = 1;
+  const int rc = zt_zlib_compress_indexed(p, n, &o, &out, &olen, &adler, &idx, &ilen);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj;
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
+  set_num(env, obj, "adler32", adler);
+  napi_set_named_property(env, obj, "index", new_u8(env, idx, ilen));
+  return obj;
+}
+
 // ---- indexed random access (include/zt_index.h) ----------------------------------
 // inflateIndexBuild(input: Uint8Array, index) -> Uint8Array (the index blob)
 napi_value inflate_index_build(napi_env env, napi_callback_info info) {
@@ -725,6 +778,9 @@ napi_value init(napi_env env, napi_value exports) {
       {"zipCompress", nullptr, zip_compress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"unzip", nullptr, unzip, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"inflateIndexBuild", nullptr, inflate_index_build, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"deflateRawIndexed", nullptr, deflate_raw_indexed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"gzipCompressIndexed", nullptr, gzip_compress_indexed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"zlibCompressIndexed", nullptr, zlib_compress_indexed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"inflateRanges", nullptr, inflate_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},

@@ -185,6 +185,10 @@ def _load():
         "zt_inflate_ranges": ([vp, sz, vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
                                P(ctypes.c_int)], ctypes.c_int),
         "zt_index_stats_read": ([P(IndexStats), ctypes.c_int], ctypes.c_int),
+        # include/zt_index.h, the write side
+        "zt_deflate_raw_indexed": ([vp, sz, P(DeflateOpts), sz, u8pp, P(sz), u8pp, P(sz)], ctypes.c_int),
+        "zt_gzip_compress_indexed": ([vp, sz, P(GzipOpts), u8pp, P(sz), P(u32), u8pp, P(sz)], ctypes.c_int),
+        "zt_zlib_compress_indexed": ([vp, sz, P(DeflateOpts), u8pp, P(sz), P(u32), u8pp, P(sz)], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -233,6 +237,12 @@ CONTAINER_BATCH_SYMBOLS = [
 # every symbol include/zt_index.h declares (checked by tests/test_index_host.py)
 INDEX_SYMBOLS = [
     "zt_inflate_index_build", "zt_inflate_range", "zt_inflate_ranges", "zt_index_stats_read",
+]
+
+
+# the write side of include/zt_index.h (checked by tests/test_deflate_index_host.py)
+DEFLATE_INDEX_SYMBOLS = [
+    "zt_deflate_raw_indexed", "zt_gzip_compress_indexed", "zt_zlib_compress_indexed",
 ]
 
 
@@ -753,6 +763,60 @@ def inflate_ranges(stream, idx, ranges, return_code=False):
         if outs[i]:
             lib.zt_free(outs[i])
     return (rc, res) if return_code else res
+
+
+def _take_pair(out, olen, idx, ilen):
+    blob = ctypes.string_at(idx, ilen.value)
+    lib.zt_free(idx)
+    return _take(out, olen), blob
+
+
+def deflate_raw_indexed(data, compression_type=2, lazy=0, level=-1, stream_start=0):
+    """zt_deflate_raw_indexed: (stream, index blob).  The stream is
+    deflate_raw's; the blob describes it placed at byte `stream_start` of the
+    buffer later given to inflate_range."""
+    b, n = _cbuf(data)
+    opts = DeflateOpts(compression_type, lazy, level)
+    out, idx = ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(ctypes.c_uint8)()
+    olen, ilen = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(lib.zt_deflate_raw_indexed(b, n, ctypes.byref(opts), stream_start, ctypes.byref(out), ctypes.byref(olen),
+                                      ctypes.byref(idx), ctypes.byref(ilen)))
+    return _take_pair(out, olen, idx, ilen)
+
+
+def gzip_compress_indexed(data, name=None, comment=None, hcrc=False, mtime=0, compression_type=2, lazy=0, level=-1):
+    """zt_gzip_compress_indexed: (member bytes, index blob); the blob's
+    stream_start is the header's length, so both go straight into
+    inflate_range."""
+    b, n = _cbuf(data)
+    o = GzipOpts()
+    o.deflate = DeflateOpts(compression_type, lazy, level)
+    o.fname, o.fcomment, o.fhcrc, o.mtime = int(name is not None), int(comment is not None), int(hcrc), mtime
+    if name is not None:
+        o.name, o.name_len = bytes(name), len(name)
+    if comment is not None:
+        o.comment, o.comment_len = bytes(comment), len(comment)
+    out, idx = ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(ctypes.c_uint8)()
+    olen, ilen = ctypes.c_size_t(), ctypes.c_size_t()
+    crc = ctypes.c_uint32()
+    _check(lib.zt_gzip_compress_indexed(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen),
+                                        ctypes.byref(crc), ctypes.byref(idx), ctypes.byref(ilen)))
+    return _take_pair(out, olen, idx, ilen)
+
+
+def zlib_compress_indexed(data, compression_type=2, lazy=0, level=-1, dictionary=None):
+    """zt_zlib_compress_indexed: (stream, index blob), stream_start 2.  A
+    preset dictionary is refused (ZT_E_ARG): the range path has none."""
+    if dictionary is not None:
+        raise ZtError(-103, "an indexed zlib stream cannot use a preset dictionary")
+    b, n = _cbuf(data)
+    o = DeflateOpts(compression_type, lazy, level)
+    out, idx = ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(ctypes.c_uint8)()
+    olen, ilen = ctypes.c_size_t(), ctypes.c_size_t()
+    adler = ctypes.c_uint32()
+    _check(lib.zt_zlib_compress_indexed(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen),
+                                        ctypes.byref(adler), ctypes.byref(idx), ctypes.byref(ilen)))
+    return _take_pair(out, olen, idx, ilen)
 
 
 def index_stats(reset=False):
