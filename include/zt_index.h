@@ -38,8 +38,9 @@
  *                                  (unit 0, or after a restart marker)
  *   the last entry is a sentinel: in_off = end_ip, out_off = total_out, ntok = flags = 0
  *
- * Not covered: streams without sync points (ZT_E_NO_INDEX; decode them with
- * zt_inflate_raw), an index *build* of streams too large for the one-call
+ * Not covered here: streams without sync points (ZT_E_NO_INDEX from these
+ * calls; zt_checkpoint.h has the checkpoint index that reads ranges of such
+ * streams), an index *build* of streams too large for the one-call
  * device decode (the _indexed writers have no such limit), device resident
  * and multi-GPU forms, the batch and zip writers, container parsing on the
  * read side (the _indexed gzip and zlib writers set stream_start themselves).

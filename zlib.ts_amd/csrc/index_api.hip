@@ -90,14 +90,7 @@ __global__ __launch_bounds__(256) void range_verify_kernel(RangeVerify P) {
   }
 }
 
-// One requested range with bytes: dec[src .. src + len) -> out[dst ..], dst
-// 256-aligned; its tiles are workgroups [tile0, tile0 + ceil(len / kGatherTile)).
-struct RangeJob {
-  uint64_t src, dst, len;
-  uint32_t tile0, pad;
-};
-constexpr uint32_t kGatherTile = 32768;
-
+// (RangeJob, kGatherTile: zt_internal.h -- the checkpoint range decode gathers the same way)
 typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
 
 // One workgroup per range and tile.  The destination is 16-byte aligned at
@@ -391,6 +384,14 @@ int ranges_impl(const uint8_t *in, size_t n, const uint8_t *idx, size_t idx_len,
 }
 
 }  // namespace
+
+int range_gather_dev(const RangeJob *d_jobs, uint32_t njobs, uint32_t tiles, const uint8_t *d_dec, uint8_t *d_out,
+                     const ChainInfo *d_info, hipStream_t s) {
+  if (tiles == 0) return ZT_OK;
+  range_gather_kernel<<<tiles, 256, 0, s>>>(d_jobs, njobs, d_dec, d_out, d_info);
+  ZT_HIP(hipGetLastError());
+  return ZT_OK;
+}
 
 }  // namespace zt
 

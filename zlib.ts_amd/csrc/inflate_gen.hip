@@ -40,6 +40,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ckpt_host.h"
 #include "inflate_simt.h"
 
 namespace zt {
@@ -303,6 +304,10 @@ struct GenParams {
   uint32_t count;
 };
 
+// TAIL: decode the overlap past a GK_HUFF stop (the speculative chain's merge
+// test).  The checkpoint range decode, whose every unit starts exactly, runs
+// without it: no bitmap, and a token slot of exactly the unit's tokens.
+template <bool TAIL>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void gen_tokenize_kernel(GenParams P) {
   __shared__ GenShared sh;
   __shared__ SpecShared spsh;
@@ -409,11 +414,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void ge
         // successor that started inside this body find where the paths merge
         ntok_stop = uni(to.ntok);
         out_stop = op;
-        bool s2 = false;
-        uint64_t e2 = 0;
-        const int r2 = tok_huffman_simt(rd, end_bit, &sh.lit, &sh.dist, to, op, &spsh, e2, nullptr, GEN_OVERLAP,
-                                        P.bm + (uint64_t)u * 2 * GEN_BM_WORDS + GEN_BM_WORDS, &s2);
-        tail_ok = r2 == 0 ? 1u : 0u;
+        if (TAIL) {
+          bool s2 = false;
+          uint64_t e2 = 0;
+          const int r2 = tok_huffman_simt(rd, end_bit, &sh.lit, &sh.dist, to, op, &spsh, e2, nullptr, GEN_OVERLAP,
+                                          P.bm + (uint64_t)u * 2 * GEN_BM_WORDS + GEN_BM_WORDS, &s2);
+          tail_ok = r2 == 0 ? 1u : 0u;
+        }
         stopped_here = true;
         break;
       }
@@ -902,7 +909,8 @@ void radix_sort64(std::vector<uint64_t> &v, uint64_t max_key) {
 // (two 1-bit codes) -- kGenDense asks the caller for that second attempt.
 constexpr int kGenDense = 3;
 static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io, size_t out_cap,
-                       size_t *out_len, size_t *end_ip, hipStream_t s, bool dense) {
+                       size_t *out_len, size_t *end_ip, hipStream_t s, bool dense,
+                       std::vector<CkEntry> *ckpt = nullptr) {
   if (n < index + (1u << 14)) return 1;
   const uint64_t bit0 = (uint64_t)index * 8, bitn = (uint64_t)n * 8;
   // ---- 1. candidates
@@ -1082,7 +1090,7 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
     ZT_HIP(hipMemcpyAsync(d_which, todo.data(), todo.size() * 4, hipMemcpyHostToDevice, s));
     gp.which = d_which;
     gp.count = (uint32_t)todo.size();
-    gen_tokenize_kernel<<<gp.count, 64, 0, s>>>(gp);
+    gen_tokenize_kernel<true><<<gp.count, 64, 0, s>>>(gp);
     ZT_HIP(hipGetLastError());
     if (!ltodo.empty()) {
       ZT_HIP(hipMemcpyAsync(d_lwhich, ltodo.data(), ltodo.size() * 4, hipMemcpyHostToDevice, s));
@@ -1271,6 +1279,27 @@ static int general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index
                 (unsigned long long)gsegs[i].len, segs[i].first, segs[i].count);
     }
   }
+  if (ckpt) {
+    // the checkpoint index (ckpt_api.hip): entry k + 1 is chain unit k's end
+    // state, at the output offset of the tokens before it; entry k's token
+    // count runs from its own state to the next one's -- unit k - 1's overlap
+    // up to the join, then unit k's tokens from the join to its stop
+    ckpt->assign(chain_end + 2, CkEntry{});
+    (*ckpt)[0].pos = bit0;
+    (*ckpt)[0].kind = GK_BLOCK;
+    for (size_t k = 0; k <= chain_end; ++k) {
+      const GenState &e = res[k].end;
+      CkEntry &x = (*ckpt)[k + 1];
+      x.pos = e.pos;
+      x.kind = e.kind;
+      x.hdr = e.kind == GK_HUFF ? e.hdr : 0;
+      x.rem = e.kind == GK_STORED ? e.rem : 0;
+      x.flags = (e.kind == GK_HUFF || e.kind == GK_STORED || e.kind == GK_SHDR) && e.bfinal ? 2u : 0u;
+      x.out_off = chain[k].out_off + res[k].out_stop - (k ? link[k].bytes : 0);
+      (*ckpt)[k].ntok = (k ? link[k].prev_cut - res[k - 1].ntok_stop : 0u) + res[k].ntok_stop - (k ? link[k].t : 0u);
+    }
+    if ((*ckpt)[chain_end + 1].out_off != total) GFALLBACK("checkpoints: the last end state is not the output's end\n");
+  }
   *out_len = total;
   *end_ip = (res[chain_end].end.pos + 7) >> 3;
   uint8_t *d_out = *d_out_io;
@@ -1365,6 +1394,33 @@ int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t inde
   int r = general_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s, false);
   if (r == kGenDense) r = general_dev(c, d_in, n, index, d_out_io, out_cap, out_len, end_ip, s, true);
   return r;
+}
+
+int inflate_general_ckpt_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out, size_t *out_len,
+                             size_t *end_ip, std::vector<CkEntry> *entries, hipStream_t s) {
+  int r = general_dev(c, d_in, n, index, d_out, 0, out_len, end_ip, s, false, entries);
+  if (r == kGenDense) {
+    *d_out = nullptr;
+    r = general_dev(c, d_in, n, index, d_out, 0, out_len, end_ip, s, true, entries);
+  }
+  return r;
+}
+
+int gen_tokenize_exact_dev(const uint8_t *d_in, uint64_t n, const GenJob *d_jobs, GenResult *d_res, uint32_t *d_tokens,
+                           uint32_t count, hipStream_t s) {
+  if (count == 0) return ZT_OK;
+  GenParams gp;
+  gp.in = d_in;
+  gp.n = n;
+  gp.jobs = d_jobs;
+  gp.res = d_res;
+  gp.which = nullptr;
+  gp.tokens = d_tokens;
+  gp.bm = nullptr;
+  gp.count = count;
+  gen_tokenize_kernel<false><<<count, 64, 0, s>>>(gp);
+  ZT_HIP(hipGetLastError());
+  return ZT_OK;
 }
 
 }  // namespace zt

@@ -684,7 +684,48 @@ __global__ __launch_bounds__(64) void copy_kernel(ResolveParams P) {
   if (lane == 0) P.seg_status[sg] = ZT_OK;
 }
 
+// copy_kernel for a segment that starts in the middle of a stream with the
+// 32 KiB of output before it at hand (the checkpoint range decode): the
+// history ring starts as those bytes -- byte i of the window is the byte
+// 32768 - i before the segment, which is ring slot i -- so a descriptor that
+// reaches behind the segment start reads the real byte at once.  No u16
+// staging, no markers and no second pass, as copy_marker_kernel needs when the
+// previous segment is still being decoded.  Same shape as copy_kernel: one
+// wave and 40 KiB of LDS per segment, four segments per CU.
+__global__ __launch_bounds__(64) void copy_window_kernel(ResolveParams P, const uint8_t *__restrict__ wins,
+                                                         const int32_t *__restrict__ seg_win) {
+  __shared__ CopyShared sh;
+  const uint32_t sg = blockIdx.x;
+  const int lane = threadIdx.x & 63;
+  if (P.info && (!P.info->ok || sg >= P.info->nseg)) return;
+  const SegJob sj = P.segs[sg];
+  const int32_t w = seg_win[sg];
+  const u32x4r *src = reinterpret_cast<const u32x4r *>(wins + (size_t)(w < 0 ? 0 : w) * RING);  // (16-byte aligned)
+  for (uint32_t i = (uint32_t)lane; i < (uint32_t)RING / 16; i += 64)
+    *reinterpret_cast<u32x4r *>(&sh.ring[i * 16]) = w < 0 ? u32x4r{0, 0, 0, 0} : src[i];
+  wave_sync();
+  const uint64_t seg_out = P.units[sj.first].out_off;
+  const ChainUnit lastu = P.units[sj.first + sj.count - 1];
+  const uint64_t n = lastu.out_off + lastu.out_len - seg_out;
+  uint8_t *out = P.out + seg_out;
+  const uint16_t *dsrc = P.desc + P.units[sj.first].desc_off;
+  if (n < (1ull << 31))
+    copy_run<uint32_t>(sh, out, dsrc, (uint32_t)n, lane);
+  else
+    copy_run<uint64_t>(sh, out, dsrc, n, lane);
+  if (lane == 0) P.seg_status[sg] = ZT_OK;
+}
+
 }  // namespace
+
+int resolve_segments_window_dev(const ResolveParams &p, const uint8_t *wins, const int32_t *seg_win, hipStream_t s) {
+  if (p.nseg == 0) return ZT_OK;
+  expand_kernel<<<p.nunits, 64, 0, s>>>(p);
+  ZT_HIP(hipGetLastError());
+  copy_window_kernel<<<p.nseg, 64, 0, s>>>(p, wins, seg_win);
+  ZT_HIP(hipGetLastError());
+  return ZT_OK;
+}
 
 int tokenize_units_dev(const TokParams &p, hipStream_t s) {
   if (p.count == 0) return ZT_OK;

@@ -93,6 +93,8 @@ enum ScratchSlot : int {
   kRangeIn = 31,    // range inflate (index_api.hip): stops | TokJob | chain | segments | ranges | ChainInfo |
                     // packed input (one upload), then TokResult; whole call (it also takes kTokens, kDeflateOrDesc and kOut)
   kRangeOut = 32,   // range inflate: packed ranges | statuses, one download; whole call
+                    // (31, 32: the checkpoint range decode of ckpt_api.hip uses them the same way, never inside the other)
+  kCkptWin = 33,    // checkpoint build (ckpt_api.hip): window offsets | window records; after the general decode, inside the call
   kScratchSlots
 };
 // Pinned host staging (DeviceCtx::h_pinned, pinned()).
@@ -689,6 +691,22 @@ inline int tok_simt_env() {
 int tokenize_units_dev(const TokParams &p, hipStream_t s);
 int resolve_segments_dev(const ResolveParams &p, hipStream_t s);
 int expand_units_dev(const ResolveParams &p, hipStream_t s);
+// One requested range with bytes (index_api.hip, ckpt_api.hip): dec[src .. src
+// + len) -> out[dst ..], dst 256-aligned; its tiles are workgroups [tile0,
+// tile0 + ceil(len / kGatherTile)) of range_gather_kernel, which does nothing
+// unless info->ok.
+struct RangeJob {
+  uint64_t src, dst, len;
+  uint32_t tile0, pad;
+};
+constexpr uint32_t kGatherTile = 32768;
+int range_gather_dev(const RangeJob *d_jobs, uint32_t njobs, uint32_t tiles, const uint8_t *d_dec, uint8_t *d_out,
+                     const ChainInfo *d_info, hipStream_t s);
+// expand_kernel (p.marker = 1), then copy_window_kernel: segment g's 32 KiB
+// history ring starts as the 32768 bytes at wins + 32768 * seg_win[g]
+// (seg_win[g] < 0: the stream's first segment, no history) -- the checkpoint
+// range decode (ckpt_api.hip)
+int resolve_segments_window_dev(const ResolveParams &p, const uint8_t *wins, const int32_t *seg_win, hipStream_t s);
 
 // A chain buffer, in a device scratch slot or its mirror in pinned staging:
 // [chain units | segment jobs | extra | unit statuses | segment statuses | tail]
@@ -803,6 +821,20 @@ struct GenSeg {        // copy segment of the general path
 };
 int inflate_general_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out_io,
                         size_t out_cap, size_t *out_len, size_t *end_ip, hipStream_t s);
+
+// The checkpoint build (include/zt_checkpoint.h, ckpt_api.hip): the general
+// path with its converged chain kept -- *entries receives one entry per unit
+// boundary (positions, kinds, output offsets, token counts; windows not yet
+// placed) and the sentinel; the output is library-owned (kOut, in *d_out).
+// Returns as inflate_general_dev does.
+struct CkEntry;
+int inflate_general_ckpt_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t index, uint8_t **d_out, size_t *out_len,
+                             size_t *end_ip, std::vector<CkEntry> *entries, hipStream_t s);
+// gen_tokenize_kernel over `count` units that all start exactly (spec = 0), one
+// wave each, without the overlap past a stop: a unit's token slot need only
+// hold its own tokens
+int gen_tokenize_exact_dev(const uint8_t *d_in, uint64_t n, const GenJob *d_jobs, GenResult *d_res, uint32_t *d_tokens,
+                           uint32_t count, hipStream_t s);
 
 int inflate_jobs_dev(const InfJob *d_jobs, InfResult *d_res, int count, hipStream_t s);
 // one device-resident stream from `index`, output malloc'd (inflate_api.cpp)

@@ -78,4 +78,37 @@ export class RawInflate {
             throw refError(e);
         }
     }
+
+    // Checkpoint index (include/zt_checkpoint.h): random access into streams
+    // WITHOUT sync points -- what zlib, pigz, Python and Node write, and the
+    // reference's own one-block output.  buildCheckpoints() decodes the stream
+    // once and returns its checkpoint blob (a Uint8Array that may be stored;
+    // span: output bytes between window checkpoints, default 1 MiB, at least
+    // 64 KiB); decompressRangeAt / decompressRangesAt then decode only from the
+    // last window checkpoint before a range.  Same conventions as the three
+    // methods above; the two kinds of blob are not interchangeable (ztStatus -61).
+    buildCheckpoints(opts = {}) {
+        try {
+            return native.inflateCkptBuild(this.input, this.streamStart, dflt(opts.span, 0));
+        } catch (e) {
+            throw refError(e);
+        }
+    }
+
+    decompressRangeAt(blob, offset, length) {
+        return this.decompressRangesAt(blob, [[offset, length]])[0];
+    }
+
+    decompressRangesAt(blob, ranges) {
+        const off = new Float64Array(ranges.length), len = new Float64Array(ranges.length);
+        for (let i = 0; i < ranges.length; i++) {
+            off[i] = ranges[i][0];
+            len[i] = ranges[i][1];
+        }
+        try {
+            return native.inflateCkptRanges(this.input, blob, off, len);
+        } catch (e) {
+            throw refError(e);
+        }
+    }
 }

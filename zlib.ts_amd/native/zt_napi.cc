@@ -16,6 +16,7 @@
 #include "../../include/zt_dict.h"
 #include "../../include/zt_container_batch.h"
 #include "../../include/zt_index.h"
+#include "../../include/zt_checkpoint.h"
 
 namespace {
 
@@ -702,7 +703,8 @@ napi_value inflate_index_build(napi_env env, napi_callback_info info) {
 
 // inflateRanges(input: Uint8Array, indexBlob: Uint8Array, offsets: Float64Array, lengths: Float64Array)
 //   -> Uint8Array[]; the first failing range throws
-napi_value inflate_ranges(napi_env env, napi_callback_info info) {
+// (ckpt: inflateCkptRanges, the same arguments with a checkpoint blob, include/zt_checkpoint.h)
+napi_value inflate_ranges_any(napi_env env, napi_callback_info info, bool ckpt) {
   napi_value a[4];
   args(env, info, a, 4);
   const uint8_t *p, *ix;
@@ -739,7 +741,9 @@ napi_value inflate_ranges(napi_env env, napi_callback_info info) {
   std::vector<uint8_t *> out(count, nullptr);
   std::vector<size_t> olen(count, 0);
   std::vector<int> st(count, 0);
-  const int rc = zt_inflate_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(), st.data());
+  const int rc = ckpt ? zt_inflate_ckpt_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(),
+                                               st.data())
+                      : zt_inflate_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(), st.data());
   if (rc) {
     for (uint8_t *o : out) zt_free(o);
     return throw_zt(env, rc);
@@ -748,6 +752,26 @@ napi_value inflate_ranges(napi_env env, napi_callback_info info) {
   napi_create_array_with_length(env, count, &arr);
   for (size_t i = 0; i < count; ++i) napi_set_element(env, arr, (uint32_t)i, new_u8(env, out[i], olen[i]));
   return arr;
+}
+
+napi_value inflate_ranges(napi_env env, napi_callback_info info) { return inflate_ranges_any(env, info, false); }
+napi_value inflate_ckpt_ranges(napi_env env, napi_callback_info info) { return inflate_ranges_any(env, info, true); }
+
+// ---- checkpoint index (include/zt_checkpoint.h) ------------------------------------
+// inflateCkptBuild(input: Uint8Array, index, span) -> Uint8Array (the checkpoint blob)
+napi_value inflate_ckpt_build(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  const int64_t index = get_i64(env, a[1], 0), span = get_i64(env, a[2], 0);
+  uint8_t *idx = nullptr;
+  size_t ilen = 0;
+  const int rc = zt_inflate_ckpt_build(p, n, index < 0 ? 0 : (size_t)index, span < 0 ? 1 : (uint64_t)span, &idx, &ilen,
+                                       nullptr, nullptr, nullptr);
+  if (rc) return throw_zt(env, rc);
+  return new_u8(env, idx, ilen);
 }
 
 napi_value device_count(napi_env env, napi_callback_info) {
@@ -782,6 +806,8 @@ napi_value init(napi_env env, napi_value exports) {
       {"gzipCompressIndexed", nullptr, gzip_compress_indexed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"zlibCompressIndexed", nullptr, zlib_compress_indexed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"inflateRanges", nullptr, inflate_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"inflateCkptBuild", nullptr, inflate_ckpt_build, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"inflateCkptRanges", nullptr, inflate_ckpt_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
   };

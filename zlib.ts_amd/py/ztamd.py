@@ -91,6 +91,12 @@ class IndexStats(ctypes.Structure):
                                                "in_bytes_uploaded", "out_bytes_decoded", "out_bytes_returned")]
 
 
+class CkptStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("builds", "range_calls", "ranges", "units_tokenized",
+                                               "in_bytes_uploaded", "out_bytes_decoded", "out_bytes_returned",
+                                               "window_bytes_uploaded")]
+
+
 def _load():
     # torch (when present) ships its own libamdhip64.so.7; loading it first makes
     # libzt.so bind to that same runtime (same SONAME) instead of starting a
@@ -185,6 +191,12 @@ def _load():
         "zt_inflate_ranges": ([vp, sz, vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
                                P(ctypes.c_int)], ctypes.c_int),
         "zt_index_stats_read": ([P(IndexStats), ctypes.c_int], ctypes.c_int),
+        # include/zt_checkpoint.h
+        "zt_inflate_ckpt_build": ([vp, sz, sz, ctypes.c_uint64, u8pp, P(sz), u8pp, P(sz), P(sz)], ctypes.c_int),
+        "zt_inflate_ckpt_range": ([vp, sz, vp, sz, ctypes.c_uint64, ctypes.c_uint64, u8pp, P(sz)], ctypes.c_int),
+        "zt_inflate_ckpt_ranges": ([vp, sz, vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
+                                    P(ctypes.c_int)], ctypes.c_int),
+        "zt_ckpt_stats_read": ([P(CkptStats), ctypes.c_int], ctypes.c_int),
         # include/zt_index.h, the write side
         "zt_deflate_raw_indexed": ([vp, sz, P(DeflateOpts), sz, u8pp, P(sz), u8pp, P(sz)], ctypes.c_int),
         "zt_gzip_compress_indexed": ([vp, sz, P(GzipOpts), u8pp, P(sz), P(u32), u8pp, P(sz)], ctypes.c_int),
@@ -243,6 +255,12 @@ INDEX_SYMBOLS = [
 # the write side of include/zt_index.h (checked by tests/test_deflate_index_host.py)
 DEFLATE_INDEX_SYMBOLS = [
     "zt_deflate_raw_indexed", "zt_gzip_compress_indexed", "zt_zlib_compress_indexed",
+]
+
+
+# every symbol include/zt_checkpoint.h declares (checked by tests/test_ckpt_host.py)
+CKPT_SYMBOLS = [
+    "zt_inflate_ckpt_build", "zt_inflate_ckpt_range", "zt_inflate_ckpt_ranges", "zt_ckpt_stats_read",
 ]
 
 
@@ -847,6 +865,104 @@ def index_entries(idx):
     ent = np.frombuffer(idx, dtype=ent_t, count=nunits + 1, offset=INDEX_HEADER_BYTES)
     return {"version": version, "nunits": nunits, "nseg": nseg, "stream_start": start, "end_ip": end_ip,
             "total_out": total}, ent
+
+
+# ---- checkpoint index (include/zt_checkpoint.h) --------------------------------------
+CKPT_HEADER_BYTES = 64
+CKPT_ENTRY_BYTES = 48
+CKPT_WINDOW_BYTES = 32768
+CKPT_WINDOW_RECORD_BYTES = 32784
+CKPT_FIXED_HDR = 1 << 62
+CKPT_KINDS = {"block": 0, "huff": 1, "stored": 2, "shdr": 3, "final": 4}
+
+
+def inflate_ckpt_build(stream, index=0, span=0, want_output=False):
+    """zt_inflate_ckpt_build: decodes the raw stream at stream[index:] once on
+    the general path and returns its checkpoint blob (bytes); span: output
+    bytes between window checkpoints (0: 1 MiB); want_output: (blob, output,
+    end ip)."""
+    b, n = _cbuf(stream)
+    idx = ctypes.POINTER(ctypes.c_uint8)()
+    ilen = ctypes.c_size_t()
+    olen = ctypes.c_size_t()
+    ip = ctypes.c_size_t()
+    if want_output:
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        _check(lib.zt_inflate_ckpt_build(b, n, index, span, ctypes.byref(idx), ctypes.byref(ilen), ctypes.byref(out),
+                                         ctypes.byref(olen), ctypes.byref(ip)))
+        return _take(idx, ilen), _take(out, olen), ip.value
+    _check(lib.zt_inflate_ckpt_build(b, n, index, span, ctypes.byref(idx), ctypes.byref(ilen), None,
+                                     ctypes.byref(olen), ctypes.byref(ip)))
+    return _take(idx, ilen)
+
+
+def inflate_ckpt_range(stream, blob, off, length):
+    """zt_inflate_ckpt_range: bytes [off, off + length) of the stream's output
+    (pread semantics: length is clamped, off past the end raises ZT_E_ARG)."""
+    b, n = _cbuf(stream)
+    ib, il = _cbuf(blob)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    olen = ctypes.c_size_t()
+    _check(lib.zt_inflate_ckpt_range(b, n, ib, il, off, length, ctypes.byref(out), ctypes.byref(olen)))
+    return _take(out, olen)
+
+
+def inflate_ckpt_ranges(stream, blob, ranges, return_code=False):
+    """zt_inflate_ckpt_ranges: [(off, len), ...] in one call.  Returns a list
+    of (status, bytes) pairs (bytes None for a failed range); return_code:
+    also the call's return code, as (code, list).  A call that fails before
+    any range is looked at (a bad blob) raises."""
+    b, n = _cbuf(stream)
+    ib, il = _cbuf(blob)
+    k = len(ranges)
+    offs = (ctypes.c_uint64 * k)(*[r[0] for r in ranges])
+    lens = (ctypes.c_uint64 * k)(*[r[1] for r in ranges])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_inflate_ckpt_ranges(b, n, ib, il, offs, lens, k, outs, olens, st)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    res = []
+    for i in range(k):
+        res.append((st[i], ctypes.string_at(outs[i], olens[i]) if st[i] == 0 else None))
+        if outs[i]:
+            lib.zt_free(outs[i])
+    return (rc, res) if return_code else res
+
+
+def ckpt_stats(reset=False):
+    """Work counters of the checkpoint calls (zt_ckpt_stats_read)."""
+    s = CkptStats()
+    _check(lib.zt_ckpt_stats_read(ctypes.byref(s), 1 if reset else 0))
+    return {f: int(getattr(s, f)) for f, _ in CkptStats._fields_}
+
+
+def ckpt_entries(blob):
+    """A checkpoint blob parsed with numpy: (header dict, entries, windows) --
+    entries a record array (pos, hdr, out_off, kind, rem, flags, ntok, win) of
+    nunits + 1 rows, the sentinel last; windows a list of (bytes, crc32) in
+    window order.  Raises ValueError on a blob that is not a checkpoint blob."""
+    import numpy as np
+
+    blob = bytes(blob)
+    if len(blob) < CKPT_HEADER_BYTES or blob[:4] != b"ZTCK":
+        raise ValueError("not a checkpoint blob")
+    version, nunits, nwin = (int(x) for x in np.frombuffer(blob, dtype="<u4", count=3, offset=4))
+    start, end_ip, total, span = (int(x) for x in np.frombuffer(blob, dtype="<u8", count=4, offset=16))
+    ent_bytes = (nunits + 1) * CKPT_ENTRY_BYTES
+    if version != 1 or len(blob) != CKPT_HEADER_BYTES + ent_bytes + nwin * CKPT_WINDOW_RECORD_BYTES:
+        raise ValueError("checkpoint blob version or length is wrong")
+    ent_t = np.dtype([("pos", "<u8"), ("hdr", "<u8"), ("out_off", "<u8"), ("kind", "<u4"), ("rem", "<u4"),
+                      ("flags", "<u4"), ("ntok", "<u4"), ("win", "<u4"), ("pad", "<u4")])
+    ent = np.frombuffer(blob, dtype=ent_t, count=nunits + 1, offset=CKPT_HEADER_BYTES)
+    wins = []
+    for w in range(nwin):
+        at = CKPT_HEADER_BYTES + ent_bytes + w * CKPT_WINDOW_RECORD_BYTES
+        wins.append((blob[at:at + CKPT_WINDOW_BYTES],
+                     int.from_bytes(blob[at + CKPT_WINDOW_BYTES:at + CKPT_WINDOW_BYTES + 4], "little")))
+    return {"version": version, "nunits": nunits, "nwin": nwin, "stream_start": start, "end_ip": end_ip,
+            "total_out": total, "span": span}, ent, wins
 
 
 class BatchStatus(int):
