@@ -68,10 +68,15 @@ __device__ __forceinline__ uint32_t len_sym(uint32_t L) {  // 0..28 (symbol - 25
 
 // ================================ 2. block_kernel ================================
 constexpr int PM_MAX = 2 * 286;  // package-merge list length bound (2m - 2)
+// words of a level's package bitmap: a bit for every list entry.  (PM_MAX / 32
+// = 17 words stopped at entry 543: from 274 used symbols on, the entries past
+// it set bits in the next level's row, and the codes came out incomplete)
+constexpr int PM_WORDS = (PM_MAX + 31) / 32;
+static_assert(PM_WORDS * 32 >= PM_MAX, "a package bit for every list entry");
 struct HufScratch {
   uint32_t key[320];              // (freq << 9) | symbol, sorted ascending (the first m are used)
   uint32_t lst[2][PM_MAX];        // package-merge lists (weights), ping-pong
-  uint32_t pkg[14][PM_MAX / 32];  // per level: which list entries are packages
+  uint32_t pkg[14][PM_WORDS];     // per level: which list entries are packages
   uint32_t items[16];             // selected items per level
   uint32_t bl_count[16];
 };
@@ -166,7 +171,11 @@ __device__ __forceinline__ void sort_keys(HufScratch &h, const uint32_t *freq_in
     if (lane * R + r < 320) h.key[lane * R + r] = key[r];
 }
 
-__device__ void huff_lengths(BlockShared *s, const uint32_t *freq_in, int n, int limit, uint8_t *len_out) {
+// (always inlined: left to the inliner, block_kernel's three calls came out
+// differently once debug_huffman_kernel called it too -- block_kernel 0.598 ->
+// 0.653 ms per GiB; inlined everywhere 0.579, profiles/huffman_audit.txt)
+__device__ __forceinline__ void huff_lengths(BlockShared *s, const uint32_t *freq_in, int n, int limit,
+                                             uint8_t *len_out) {
   const int lane = threadIdx.x & 63;
   HufScratch &h = s->huf;
   for (int i = lane; i < n; i += 64) len_out[i] = 0;
@@ -208,7 +217,7 @@ __device__ void huff_lengths(BlockShared *s, const uint32_t *freq_in, int n, int
   const uint32_t mm = m, cap = 2 * mm - 2;
   for (uint32_t i = lane; i < mm; i += 64) h.lst[0][i] = h.key[i] >> 9;
   for (int j = 0; j < limit - 1; ++j)
-    for (uint32_t w = lane; w < PM_MAX / 32; w += 64) h.pkg[j][w] = 0;
+    for (uint32_t w = lane; w < PM_WORDS; w += 64) h.pkg[j][w] = 0;
   wsync();
   uint32_t lp = mm;  // length of the previous level's list
   for (int j = 1; j < limit; ++j) {
@@ -1661,7 +1670,67 @@ __global__ __launch_bounds__(1024) void scan_sizes(const uint32_t *__restrict__ 
   if (t == 1023) off[n] = base + part[1023];
 }
 
+// block_kernel's two Huffman device functions on histograms handed in
+// (zt_debug_huffman): one wave per histogram, staged in LDS as block_kernel's
+// own are
+__global__ __launch_bounds__(64) void debug_huffman_kernel(const uint32_t *__restrict__ freq, uint32_t n,
+                                                           uint32_t limit, uint8_t *__restrict__ lens,
+                                                           uint32_t *__restrict__ codes) {
+  __shared__ BlockShared sh;
+  BlockShared *s = &sh;
+  const uint32_t lane = threadIdx.x;
+  const size_t base = (size_t)blockIdx.x * n;
+  for (uint32_t i = lane; i < 288; i += 64) s->lit_hist[i] = i < n ? freq[base + i] : 0u;
+  wsync();
+  huff_lengths(s, s->lit_hist, (int)n, (int)limit, s->lit_len);
+  huff_codes(s->lit_len, (int)n, s->lit_code);
+  for (uint32_t i = lane; i < n; i += 64) {
+    lens[base + i] = s->lit_len[i];
+    codes[base + i] = s->lit_code[i];
+  }
+}
+
 }  // namespace
+
+// huff_lengths + huff_codes on host histograms (zt_internal.h)
+extern "C" int zt_debug_huffman(const uint32_t *freqs, uint32_t count, uint32_t n, uint32_t limit, uint8_t *lens,
+                                uint32_t *codes) {
+  if (!freqs || !lens || !codes || count == 0 || count > (1u << 20) || n < 2 || n > 286 ||
+      (limit != 7 && limit != 15) || n > (1u << limit))
+    return set_error(ZT_E_ARG, "zt_debug_huffman: bad argument");
+  // the sort key is freq << 9 | symbol in 32 bits, and the package weights
+  // (below 15 times a histogram's sum) are 32-bit sums
+  for (uint32_t h = 0; h < count; ++h) {
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+      const uint32_t f = freqs[(size_t)h * n + i];
+      if (f >= (1u << 23)) return set_error(ZT_E_ARG, "zt_debug_huffman: frequency of 2^23 or more");
+      sum += f;
+    }
+    if (sum >= (1u << 27)) return set_error(ZT_E_ARG, "zt_debug_huffman: histogram sum of 2^27 or more");
+  }
+  DeviceCtx *c;
+  ZT_TRY(get_ctx(&c));
+  std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+  hipStream_t s = c->stream;
+  const size_t total = (size_t)count * n;
+  uint32_t *d_freq = nullptr, *d_codes = nullptr;
+  uint8_t *d_lens = nullptr;
+  ZT_TRY(scratch_carved(c, kDeflateOrDesc, [&](void *base) {
+    Carve cv(base);
+    d_freq = cv.take<uint32_t>(total);
+    d_codes = cv.take<uint32_t>(total);
+    d_lens = cv.take<uint8_t>(total);
+    return cv.bytes();
+  }));
+  ZT_HIP(hipMemcpyAsync(d_freq, freqs, total * 4, hipMemcpyHostToDevice, s));
+  debug_huffman_kernel<<<count, 64, 0, s>>>(d_freq, n, limit, d_lens, d_codes);
+  ZT_HIP(hipGetLastError());
+  ZT_HIP(hipMemcpyAsync(lens, d_lens, total, hipMemcpyDeviceToHost, s));
+  ZT_HIP(hipMemcpyAsync(codes, d_codes, total * 4, hipMemcpyDeviceToHost, s));
+  ZT_HIP(hipStreamSynchronize(s));
+  return ZT_OK;
+}
 
 int deflate_post_run(const DeflateParams &P, uint64_t *boff, hipStream_t s) {
   if (P.opt) {

@@ -482,6 +482,15 @@ extern "C" int zt_debug_match_modes(uint64_t out[2]);
 // u32 to u16 (out[0]) and from u16 to u32 (out[1]) since the last call; reads
 // and clears the device counter
 extern "C" int zt_debug_head_formats(uint64_t out[2]);
+// debug (deflate_post.hip): block_kernel's huff_lengths and huff_codes on
+// `count` histograms of n <= 286 frequencies each (freqs[count * n]), one wave
+// per histogram: code lengths limited to `limit` (7 or 15; 2^limit >= n) in
+// lens[count * n], len << 16 | bit-reversed canonical code (0: unused) in
+// codes[count * n].  ZT_E_ARG for a frequency of 2^23 or more (the sort key is
+// freq << 9 | symbol) or a histogram summing to 2^27 or more (package weights
+// are 32-bit sums); block_kernel's own histograms sum to a block's tokens
+extern "C" int zt_debug_huffman(const uint32_t *freqs, uint32_t count, uint32_t n, uint32_t limit, uint8_t *lens,
+                                uint32_t *codes);
 // deflate (deflate.hip): one stream of n bytes at d_in (halo bytes of history
 // in front of it, final_: the last call of the stream) in one pipeline;
 // scratch of deflate_scratch_bytes(n), output of at most deflate_bound_bytes(n)

@@ -156,6 +156,7 @@ def _load():
         # debug (csrc/zt_internal.h)
         "zt_debug_match_modes": ([P(ctypes.c_uint64)], ctypes.c_int),
         "zt_debug_head_formats": ([P(ctypes.c_uint64)], ctypes.c_int),
+        "zt_debug_huffman": ([vp, u32, u32, u32, vp, vp], ctypes.c_int),
         "zt_debug_chain": ([vp, vp, vp, u32, ctypes.c_uint64, ctypes.c_uint64, u32, vp, vp, vp], ctypes.c_int),
         "zt_debug_chain_host": ([vp, vp, vp, u32, vp, vp, vp, P(u32), P(ctypes.c_int)], ctypes.c_int),
         # include/zt_zipcrypto.h
@@ -1154,6 +1155,25 @@ def debug_head_formats():
     v = (ctypes.c_uint64 * 2)()
     _check(lib.zt_debug_head_formats(v))
     return int(v[0]), int(v[1])
+
+
+def debug_huffman(freqs, n, limit):
+    """The deflate block kernel's code construction on given histograms: freqs
+    is count * n frequencies (count histograms of n <= 286 symbols), limit 7 or
+    15.  Returns (lens uint8[count, n], codes uint32[count, n]); a code is
+    len << 16 | the canonical code bit-reversed, 0 for an unused symbol.
+    Frequencies of 2^23 or more and histograms summing to 2^27 or more are
+    rejected (ZT_E_ARG)."""
+    import numpy as np
+
+    f = np.ascontiguousarray(freqs, dtype=np.uint32).reshape(-1)
+    if n <= 0 or f.size == 0 or f.size % n:
+        raise ValueError("freqs must hold a whole number of n-entry histograms")
+    count = f.size // n
+    lens = np.zeros((count, n), dtype=np.uint8)
+    codes = np.zeros((count, n), dtype=np.uint32)
+    _check(lib.zt_debug_huffman(f.ctypes.data, count, n, limit, lens.ctypes.data, codes.ctypes.data))
+    return lens, codes
 
 
 def debug_chain(res, restart, tok_off, out_cap, desc_cap, max_seg, host=False):
