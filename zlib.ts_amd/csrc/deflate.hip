@@ -395,7 +395,6 @@ struct MatchShared {
 };
 static_assert(sizeof(MatchShared) <= 160 * 1024, "MatchShared fits the CU's LDS");
 static_assert(offsetof(MatchShared, head32) % 8 == 0, "head_convert moves u32 heads in pairs");
-
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
 // operations, not for its global loads (the next sub-chunk's prefetch stays
 // in flight) nor its global stores (res[] is read by later kernels only).
@@ -581,6 +580,88 @@ __device__ void chain_link(MatchShared *s, uint32_t lo, uint32_t hi, Key key) {
       __hip_atomic_store(T == 0 ? &s->linked : &s->linked4, done < hi ? done : hi, __ATOMIC_RELEASE,
                          __HIP_MEMORY_SCOPE_WORKGROUP);
   }
+}
+
+// The same links for ng whole groups of CL_U steps from lo on: every position
+// of a whole group is in range, so no lane needs a dummy target or a clamped
+// address -- positions advance by adds, and the slot index is masked for the
+// wrap only (lo is any position: a group may straddle the ring's end).  The
+// progress word goes out as a plain LDS store behind the group's link stores:
+// the LDS applies one wave's operations in issue order (the exchanges above
+// rely on it; stores and a flag store after them: tools/micro/
+// lds_publish_order.hip), so no wait drains the link stores and the next
+// group's hash reads before the next exchanges issue.  The store is inline
+// assembly with a memory clobber: the compiler neither moves it nor puts a
+// wait in front of it.  The hash reads run one group ahead and
+// past the last group read slots that are not used (in bounds: the index is
+// masked).
+template <int T, bool F16>
+__device__ __forceinline__ void chain_link_groups(MatchShared *s, uint32_t lo, uint32_t ng) {
+  const uint32_t lane = threadIdx.x & 63;
+  constexpr uint32_t G = CL_U * 64;
+  auto slot = [&](uint32_t q) -> uint16_t * { return T == 0 ? &s->prev[ridx(q)] : &s->link4[q & (DF_SUB - 1)]; };
+  uint32_t p = lo + lane;  // this lane's position in the group's first step
+  uint32_t hq[CL_U];
+#pragma unroll
+  for (int j = 0; j < CL_U; ++j) hq[j] = *slot(p + 64 * j);
+  // (the first hashes are waited for here, once per call: with loads pending
+  // at the loop's entry the compiler's waits at its head, which must hold for
+  // the entry and the back edge alike, would count the link stores of the
+  // group before as done as well)
+  static_assert(CL_U == 8, "the statement below names 8 hashes");
+  __asm__ volatile("" : "+v"(hq[0]), "+v"(hq[1]), "+v"(hq[2]), "+v"(hq[3]), "+v"(hq[4]), "+v"(hq[5]), "+v"(hq[6]), "+v"(hq[7]));
+  for (uint32_t g = 0; g < ng; ++g, p += G) {
+    uint32_t d[CL_U];  // the exchanged heads, then the distances to them
+    if (T == 0 && F16) {
+      uint32_t sh[CL_U];
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) {
+        const uint32_t q = p + 64 * j;
+        sh[j] = (hq[j] & 1) * 16;
+        const uint32_t a = (uint32_t)(uintptr_t)&s->head[hq[j] >> 1], clr = 0xFFFFu << sh[j], set = (q & 0xFFFFu) << sh[j];
+        __asm__ volatile("ds_mskor_rtn_b32 %0, %1, %2, %3" : "=v"(d[j]) : "v"(a), "v"(clr), "v"(set) : "memory");
+      }
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) hq[j] = *slot(p + G + 64 * j);
+      // (the wait covers the hashes too, and names them: the compiler's own
+      // counted waits for them at the next group's exchanges, which it cannot
+      // see, would each wait for one more of this group's link stores)
+      __asm__ volatile("s_waitcnt lgkmcnt(0)"
+                       : "+v"(d[0]), "+v"(d[1]), "+v"(d[2]), "+v"(d[3]), "+v"(d[4]), "+v"(d[5]), "+v"(d[6]),
+                         "+v"(d[7]), "+v"(hq[0]), "+v"(hq[1]), "+v"(hq[2]), "+v"(hq[3]), "+v"(hq[4]), "+v"(hq[5]),
+                         "+v"(hq[6]), "+v"(hq[7])::"memory");
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) d[j] = (p + 64 * j - (d[j] >> sh[j])) & 0xFFFFu;  // (exact: head_sweep)
+    } else {
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) d[j] = atomicExch(T == 0 ? &s->head32[hq[j]] : &s->head4[hq[j]], p + 64 * j);
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) hq[j] = *slot(p + G + 64 * j);
+#pragma unroll
+      for (int j = 0; j < CL_U; ++j) d[j] = p + 64 * j - d[j];
+    }
+#pragma unroll
+    for (int j = 0; j < CL_U; ++j) *slot(p + 64 * j) = (uint16_t)(d[j] <= (uint32_t)DF_MAXDIST ? d[j] : 0u);
+    // (a store the compiler does not count only makes its counted waits
+    // stronger; it has no result to wait for)
+    if (lane == 0) {
+      const uint32_t a = (uint32_t)(uintptr_t)(T == 0 ? &s->linked : &s->linked4), done = p + G;  // (lane 0: p = lo + g * G)
+      __asm__ volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(done) : "memory");
+    }
+  }
+}
+
+// chain_link, whole groups first and the ragged rest as before (lean = false,
+// ZT_DF_LINK=0: all of it as before)
+template <int T, bool F16 = false>
+__device__ __forceinline__ void link_range(MatchShared *s, uint32_t lo, uint32_t hi, Key key, bool lean) {
+  if (lean) {
+    const uint32_t ng = (hi - lo) / (CL_U * 64);
+    if (ng) chain_link_groups<T, F16>(s, lo, ng);
+    lo += ng * (CL_U * 64);
+    if (lo == hi) return;
+  }
+  chain_link<T, F16>(s, lo, hi, key);
 }
 
 // u16 heads hold rel positions modulo 2^16: every HEAD_SWEEP sub-chunks, at
@@ -1335,11 +1416,11 @@ __device__ __forceinline__ void match_body(const DeflateParams P, const DictView
     // final (positions only read links of older ones)
     if (t < 64 && link) {
       if (fmt16)
-        chain_link<0, true>(&s, inserted, ih, key);
+        link_range<0, true>(&s, inserted, ih, key, P.link != 0);
       else
-        chain_link<0, false>(&s, inserted, ih, key);
+        link_range<0, false>(&s, inserted, ih, key, P.link != 0);
     }
-    if (t >= 64 && t < 128 && link) chain_link<1>(&s, inserted, ih, key);
+    if (t >= 64 && t < 128 && link) link_range<1>(&s, inserted, ih, key, P.link != 0);
 #ifdef ZT_DF_TIME
     uint64_t tl;
     DF_T(tl);
@@ -1463,6 +1544,7 @@ struct DeflateLevel {
   int mq_thr = 0;  // per-block queued measurement (DeflateParams; 0: never)
   int heads = 0;   // chain-head format (DeflateParams; 0: per block)
   int parse_serial = 0;  // the serial window walk in parse / price (DeflateParams)
+  int link = 1;    // the link waves' lean groups and undrained progress (DeflateParams; 0: the former link)
 };
 
 // the level table: a function of the level alone (level_params applies the
@@ -1550,6 +1632,10 @@ static DeflateLevel level_params(int level) {
   // parse_kernel and price_kernel (the reference the lane-parallel walk is
   // tested against); the streams do not depend on it
   if (const char *e = getenv("ZT_PARSE_SERIAL")) L.parse_serial = atoi(e) != 0;
+  // A/B and test hook: ZT_DF_LINK=0: the match kernel's former serial link
+  // (bounds selects in every group, a drained release store per group); the
+  // streams do not depend on it
+  if (const char *e = getenv("ZT_DF_LINK")) L.link = atoi(e) != 0;
   return L;
 }
 
@@ -1679,6 +1765,7 @@ static DeflateParams deflate_params(int level, int ctype, uint32_t nblocks, cons
   P.mq_thr = L.mq_thr;
   P.heads = L.heads;
   P.parse_serial = L.parse_serial;
+  P.link = L.link;
   P.ctype = ctype;
   P.opt = L.opt && ctype == 2;
   // classify_kernel runs for the best-of-three block choice (compressionType

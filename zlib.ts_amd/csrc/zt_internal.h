@@ -381,6 +381,10 @@ struct DeflateParams {
   // (parse_block_regs) instead of lane-parallel (ZT_PARSE_SERIAL; the streams
   // do not depend on it)
   int parse_serial;
+  // 1: match_kernel's link waves take whole groups of steps without bounds
+  // selects and publish their progress without draining their LDS queue; 0:
+  // the former link throughout (ZT_DF_LINK=0; the streams do not depend on it)
+  int link;
   // batch of independent streams (zt_deflate_batch_dev): stream f occupies
   // whole blocks from a 32 KiB-aligned offset; per block the [start, end) of
   // its stream (relative to halo = 0), or null for one stream of n bytes
