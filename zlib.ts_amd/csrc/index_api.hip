@@ -97,7 +97,10 @@ typedef unsigned int u32x4g __attribute__((ext_vector_type(4)));
 // every tile start, so the body goes out as 16-byte stores; each comes from
 // the two aligned 16-byte source words around it, shifted by the range's
 // source misalignment (uniform in the workgroup).  The last len % 16 bytes of
-// a range go byte by byte.
+// a range go byte by byte.  (A job whose destination is not 16-byte aligned --
+// the pieces of a BGZF range, packed back to back: bgzf_api.hip -- sends the
+// bytes up to the next 16-byte boundary one by one first; `out` itself is
+// aligned, so the ranges of the index calls have none.)
 __global__ __launch_bounds__(256) void range_gather_kernel(const RangeJob *__restrict__ jobs, uint32_t njobs,
                                                            const uint8_t *__restrict__ dec, uint8_t *__restrict__ out,
                                                            const ChainInfo *__restrict__ info) {
@@ -113,9 +116,15 @@ __global__ __launch_bounds__(256) void range_gather_kernel(const RangeJob *__res
   const RangeJob j = jobs[lo];
   const uint64_t o0 = (uint64_t)(blockIdx.x - j.tile0) * kGatherTile;
   if (o0 >= j.len) return;
-  const uint32_t n = (uint32_t)(j.len - o0 < kGatherTile ? j.len - o0 : kGatherTile);
+  uint32_t n = (uint32_t)(j.len - o0 < kGatherTile ? j.len - o0 : kGatherTile);
   const uint8_t *s = dec + j.src + o0;
   uint8_t *d = out + j.dst + o0;
+  const uint32_t to16 = (uint32_t)((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15);
+  const uint32_t lead = to16 < n ? to16 : n;
+  for (uint32_t i = threadIdx.x; i < lead; i += 256) d[i] = s[i];
+  s += lead;
+  d += lead;
+  n -= lead;
   const uint32_t body = n & ~15u;
   const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(s) & 15);
   const u32x4g *sa = reinterpret_cast<const u32x4g *>(s - sh);

@@ -103,15 +103,19 @@ __global__ void q_bytes_kernel(uint8_t *dst, uint64_t v, uint32_t n) {
 }
 
 // one workgroup per member: prefix, body, trailer (CRC-32 + ISIZE little
-// endian, or Adler-32 big endian)
+// endian, or Adler-32 big endian).  patch > 0 (BGZF, bgzf_api.hip): prefix
+// bytes [patch, patch + 2) are the member's own size - 1, little endian, in
+// place of the shared prefix's
 __global__ __launch_bounds__(256) void frame_members_kernel(const FrameItem *__restrict__ items,
                                                             const uint8_t *__restrict__ prefix, uint32_t plen,
                                                             uint32_t trailer, const uint8_t *__restrict__ body,
                                                             const uint32_t *__restrict__ sums,
-                                                            uint8_t *__restrict__ out) {
+                                                            uint8_t *__restrict__ out, uint32_t patch) {
   const FrameItem it = items[blockIdx.x];
   uint8_t *o = out + it.out_off;
-  for (uint32_t i = threadIdx.x; i < plen; i += 256) o[i] = prefix[i];
+  const uint32_t bsize = plen + it.body_len + trailer - 1;
+  for (uint32_t i = threadIdx.x; i < plen; i += 256)
+    o[i] = (patch && i - patch < 2) ? (uint8_t)(bsize >> (8 * (i - patch))) : prefix[i];
   const uint8_t *b = body + it.body_off;
   uint8_t *ob = o + plen;
   // (body and destination offsets are arbitrary: dwords read unaligned by
@@ -145,9 +149,11 @@ __global__ __launch_bounds__(256) void frame_members_kernel(const FrameItem *__r
 }  // namespace
 
 int frame_members_dev(const FrameItem *d_items, uint32_t count, const uint8_t *d_prefix, uint32_t plen,
-                      uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s) {
+                      uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s,
+                      uint32_t patch) {
   if (!count) return ZT_OK;
-  frame_members_kernel<<<count, 256, 0, s>>>(d_items, d_prefix, plen, trailer, d_body, d_sums, d_out);
+  if (patch && patch + 2 > plen) return set_error(ZT_E_ARG, "size patch outside the prefix");
+  frame_members_kernel<<<count, 256, 0, s>>>(d_items, d_prefix, plen, trailer, d_body, d_sums, d_out, patch);
   ZT_HIP(hipGetLastError());
   return ZT_OK;
 }

@@ -243,8 +243,11 @@ struct FrameItem {
   uint32_t body_len;
   uint32_t isize;
 };
+// patch > 0 (BGZF's BSIZE, bgzf_api.hip): prefix bytes [patch, patch + 2) of
+// item k become its size - 1 (prefix + body + trailer), little endian
 int frame_members_dev(const FrameItem *d_items, uint32_t count, const uint8_t *d_prefix, uint32_t plen,
-                      uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s);
+                      uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s,
+                      uint32_t patch = 0);
 bool slab_release(void *p);
 // fn(0 .. count-1) over a few host threads when total_bytes is large.
 // memcpy into pinned staging with streaming stores (xfer.cpp)

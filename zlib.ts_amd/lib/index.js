@@ -11,6 +11,7 @@ export { Deflate } from './Deflate.js';
 export { Inflate } from './Inflate.js';
 export { Zip, ZipCompressionMethod, ZipOperatingSystem, ZipFlags } from './Zip.js';
 export { Unzip } from './Unzip.js';
+export { BGZip, BGUnzip, bgzfVirtualOffset, BGZF_BLOCK_MAX } from './BGZF.js';
 import native from './native.js';
 export { ZT } from './native.js';
 export const deviceCount = () => native.deviceCount();

@@ -14,13 +14,15 @@ try {
 }
 export default addon;
 
-// libzt status codes (include/zt.h, include/zt_index.h)
+// libzt status codes (include/zt.h, include/zt_index.h, include/zt_bgzf.h)
 export const ZT = {
     INVALID_COMPRESSION_TYPE: -1,
     INPUT_BROKEN: -10,
     NO_INDEX: -60,
     INDEX: -61,
     INDEX_MISMATCH: -62,
+    BGZF_FORMAT: -70,
+    BGZF_INDEX: -71,
 };
 
 // `a ?? b` (Node 12 has no nullish coalescing)

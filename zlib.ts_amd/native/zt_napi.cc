@@ -17,6 +17,7 @@
 #include "../../include/zt_container_batch.h"
 #include "../../include/zt_index.h"
 #include "../../include/zt_checkpoint.h"
+#include "../../include/zt_bgzf.h"
 
 namespace {
 
@@ -701,6 +702,42 @@ napi_value inflate_index_build(napi_env env, napi_callback_info info) {
   return new_u8(env, idx, ilen);
 }
 
+// a Float64Array of non-negative integers (offsets, lengths) as uint64
+bool get_offsets(napi_env env, napi_value v, std::vector<uint64_t> *dst) {
+  bool is_ta = false;
+  napi_is_typedarray(env, v, &is_ta);
+  napi_typedarray_type t = napi_uint8_array;
+  size_t cnt = 0, boff = 0;
+  void *data = nullptr;
+  napi_value ab;
+  if (is_ta) napi_get_typedarray_info(env, v, &t, &cnt, &data, &ab, &boff);
+  if (!is_ta || t != napi_float64_array) {
+    napi_throw_type_error(env, nullptr, "expected a Float64Array");
+    return false;
+  }
+  const double *d = static_cast<const double *>(data);
+  for (size_t i = 0; i < cnt; ++i) {
+    if (!(d[i] >= 0) || d[i] > 9007199254740992.0) {
+      napi_throw_range_error(env, nullptr, "offset and length must be non-negative integers");
+      return false;
+    }
+    dst->push_back((uint64_t)d[i]);
+  }
+  return true;
+}
+
+// `count` outputs of a ranges call as Uint8Array[]; a failed call throws
+napi_value ranges_result(napi_env env, int rc, std::vector<uint8_t *> &out, const std::vector<size_t> &olen) {
+  if (rc) {
+    for (uint8_t *o : out) zt_free(o);
+    return throw_zt(env, rc);
+  }
+  napi_value arr;
+  napi_create_array_with_length(env, out.size(), &arr);
+  for (size_t i = 0; i < out.size(); ++i) napi_set_element(env, arr, (uint32_t)i, new_u8(env, out[i], olen[i]));
+  return arr;
+}
+
 // inflateRanges(input: Uint8Array, indexBlob: Uint8Array, offsets: Float64Array, lengths: Float64Array)
 //   -> Uint8Array[]; the first failing range throws
 // (ckpt: inflateCkptRanges, the same arguments with a checkpoint blob, include/zt_checkpoint.h)
@@ -711,28 +748,7 @@ napi_value inflate_ranges_any(napi_env env, napi_callback_info info, bool ckpt) 
   size_t n, in;
   if (!get_u8(env, a[0], &p, &n) || !get_u8(env, a[1], &ix, &in)) return nullptr;
   std::vector<uint64_t> off, len;
-  for (int k = 0; k < 2; ++k) {
-    bool is_ta = false;
-    napi_is_typedarray(env, a[2 + k], &is_ta);
-    napi_typedarray_type t = napi_uint8_array;
-    size_t cnt = 0, boff = 0;
-    void *data = nullptr;
-    napi_value ab;
-    if (is_ta) napi_get_typedarray_info(env, a[2 + k], &t, &cnt, &data, &ab, &boff);
-    if (!is_ta || t != napi_float64_array) {
-      napi_throw_type_error(env, nullptr, "expected a Float64Array");
-      return nullptr;
-    }
-    std::vector<uint64_t> &dst = k ? len : off;
-    const double *d = static_cast<const double *>(data);
-    for (size_t i = 0; i < cnt; ++i) {
-      if (!(d[i] >= 0) || d[i] > 9007199254740992.0) {
-        napi_throw_range_error(env, nullptr, "offset and length must be non-negative integers");
-        return nullptr;
-      }
-      dst.push_back((uint64_t)d[i]);
-    }
-  }
+  if (!get_offsets(env, a[2], &off) || !get_offsets(env, a[3], &len)) return nullptr;
   if (off.size() != len.size()) {
     napi_throw_range_error(env, nullptr, "one length per offset");
     return nullptr;
@@ -744,14 +760,7 @@ napi_value inflate_ranges_any(napi_env env, napi_callback_info info, bool ckpt) 
   const int rc = ckpt ? zt_inflate_ckpt_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(),
                                                st.data())
                       : zt_inflate_ranges(p, n, ix, in, off.data(), len.data(), count, out.data(), olen.data(), st.data());
-  if (rc) {
-    for (uint8_t *o : out) zt_free(o);
-    return throw_zt(env, rc);
-  }
-  napi_value arr;
-  napi_create_array_with_length(env, count, &arr);
-  for (size_t i = 0; i < count; ++i) napi_set_element(env, arr, (uint32_t)i, new_u8(env, out[i], olen[i]));
-  return arr;
+  return ranges_result(env, rc, out, olen);
 }
 
 napi_value inflate_ranges(napi_env env, napi_callback_info info) { return inflate_ranges_any(env, info, false); }
@@ -772,6 +781,118 @@ napi_value inflate_ckpt_build(napi_env env, napi_callback_info info) {
                                        nullptr, nullptr, nullptr);
   if (rc) return throw_zt(env, rc);
   return new_u8(env, idx, ilen);
+}
+
+// ---- BGZF (include/zt_bgzf.h) -----------------------------------------------------
+// bgzfCompress(input, compressionType, level, blockSize, wantIndex) -> {output, gzi?}
+napi_value bgzf_compress(napi_env env, napi_callback_info info) {
+  napi_value a[5];
+  args(env, info, a, 5);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  zt_bgzf_opts o;
+  o.deflate.compression_type = (int)get_i64(env, a[1], 2);
+  o.deflate.lazy = 0;
+  o.deflate.level = (int)get_i64(env, a[2], -1);
+  o.block_size = get_u32(env, a[3], 0);
+  bool want = false;
+  napi_get_value_bool(env, a[4], &want);
+  uint8_t *out = nullptr, *gzi = nullptr;
+  size_t olen = 0, glen = 0;
+  const int rc = zt_bgzf_compress(p, n, &o, &out, &olen, want ? &gzi : nullptr, want ? &glen : nullptr);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj;
+  napi_create_object(env, &obj);
+  napi_set_named_property(env, obj, "output", new_u8(env, out, olen));
+  if (want) napi_set_named_property(env, obj, "gzi", new_u8(env, gzi, glen));
+  return obj;
+}
+
+// bgzfIndex(input) -> Uint8Array (the .gzi); bgzfDecompress(input) -> Uint8Array
+napi_value bgzf_index(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  uint8_t *gzi = nullptr;
+  size_t glen = 0;
+  const int rc = zt_bgzf_index(p, n, &gzi, &glen, nullptr);
+  if (rc) return throw_zt(env, rc);
+  return new_u8(env, gzi, glen);
+}
+
+napi_value bgzf_decompress(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  uint8_t *out = nullptr;
+  size_t olen = 0;
+  const int rc = zt_bgzf_decompress(p, n, &out, &olen, nullptr);
+  if (rc) return throw_zt(env, rc);
+  return new_u8(env, out, olen);
+}
+
+// bgzfReadRanges(input, gzi: Uint8Array | null, offsets: Float64Array, lengths: Float64Array)
+//   -> Uint8Array[]; the first failing range throws
+napi_value bgzf_read_ranges(napi_env env, napi_callback_info info) {
+  napi_value a[4];
+  args(env, info, a, 4);
+  const uint8_t *p, *g;
+  size_t n, gn;
+  bool has_gzi;
+  if (!get_u8(env, a[0], &p, &n) || !get_dict(env, a[1], &g, &gn, &has_gzi)) return nullptr;
+  std::vector<uint64_t> off, len;
+  if (!get_offsets(env, a[2], &off) || !get_offsets(env, a[3], &len)) return nullptr;
+  if (off.size() != len.size()) {
+    napi_throw_range_error(env, nullptr, "one length per offset");
+    return nullptr;
+  }
+  const size_t count = off.size();
+  std::vector<uint8_t *> out(count, nullptr);
+  std::vector<size_t> olen(count, 0);
+  std::vector<int> st(count, 0);
+  static const uint8_t none = 0;  // (an empty Uint8Array may carry a null pointer)
+  const int rc = zt_bgzf_read_ranges(p, n, has_gzi ? (g ? g : &none) : nullptr, gn, off.data(), len.data(), count,
+                                     out.data(), olen.data(), st.data());
+  return ranges_result(env, rc, out, olen);
+}
+
+// bgzfReadVirtual(input, begs: BigUint64Array, ends: BigUint64Array) -> Uint8Array[]
+napi_value bgzf_read_virtual(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  const uint8_t *p;
+  size_t n;
+  if (!get_u8(env, a[0], &p, &n)) return nullptr;
+  std::vector<uint64_t> v[2];
+  for (int k = 0; k < 2; ++k) {
+    bool is_ta = false;
+    napi_is_typedarray(env, a[1 + k], &is_ta);
+    napi_typedarray_type t = napi_uint8_array;
+    size_t cnt = 0, boff = 0;
+    void *data = nullptr;
+    napi_value ab;
+    if (is_ta) napi_get_typedarray_info(env, a[1 + k], &t, &cnt, &data, &ab, &boff);
+    if (!is_ta || t != napi_biguint64_array) {
+      napi_throw_type_error(env, nullptr, "expected a BigUint64Array");
+      return nullptr;
+    }
+    v[k].assign(static_cast<const uint64_t *>(data), static_cast<const uint64_t *>(data) + cnt);
+  }
+  if (v[0].size() != v[1].size()) {
+    napi_throw_range_error(env, nullptr, "one end per begin");
+    return nullptr;
+  }
+  const size_t count = v[0].size();
+  std::vector<uint8_t *> out(count, nullptr);
+  std::vector<size_t> olen(count, 0);
+  std::vector<int> st(count, 0);
+  const int rc = zt_bgzf_read_virtual(p, n, v[0].data(), v[1].data(), count, out.data(), olen.data(), st.data());
+  return ranges_result(env, rc, out, olen);
 }
 
 napi_value device_count(napi_env env, napi_callback_info) {
@@ -808,6 +929,11 @@ napi_value init(napi_env env, napi_value exports) {
       {"inflateRanges", nullptr, inflate_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"inflateCkptBuild", nullptr, inflate_ckpt_build, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"inflateCkptRanges", nullptr, inflate_ckpt_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"bgzfCompress", nullptr, bgzf_compress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"bgzfIndex", nullptr, bgzf_index, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"bgzfDecompress", nullptr, bgzf_decompress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"bgzfReadRanges", nullptr, bgzf_read_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"bgzfReadVirtual", nullptr, bgzf_read_virtual, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
   };

@@ -18,7 +18,8 @@ ERRORS = {
     -30: "ZT_E_GZIP_SIGNATURE", -31: "ZT_E_GZIP_METHOD", -32: "ZT_E_GZIP_HCRC", -33: "ZT_E_GZIP_CRC32",
     -34: "ZT_E_GZIP_ISIZE", -40: "ZT_E_ZLIB_METHOD", -41: "ZT_E_ZLIB_FCHECK", -42: "ZT_E_ZLIB_FDICT",
     -43: "ZT_E_ZLIB_ADLER", -44: "ZT_E_ZLIB_DICTID", -50: "ZT_E_ZIP_FORMAT", -51: "ZT_E_ZIP_CRC", -52: "ZT_E_ZIP_ENCRYPTED",
-    -60: "ZT_E_NO_INDEX", -61: "ZT_E_INDEX", -62: "ZT_E_INDEX_MISMATCH", -100: "ZT_E_NO_DEVICE",
+    -60: "ZT_E_NO_INDEX", -61: "ZT_E_INDEX", -62: "ZT_E_INDEX_MISMATCH", -70: "ZT_E_BGZF_FORMAT",
+    -71: "ZT_E_BGZF_INDEX", -100: "ZT_E_NO_DEVICE",
     -101: "ZT_E_HIP", -102: "ZT_E_NOMEM", -103: "ZT_E_ARG", -104: "ZT_E_INTERNAL",
 }
 
@@ -95,6 +96,20 @@ class CkptStats(ctypes.Structure):
     _fields_ = [(f, ctypes.c_uint64) for f in ("builds", "range_calls", "ranges", "units_tokenized",
                                                "in_bytes_uploaded", "out_bytes_decoded", "out_bytes_returned",
                                                "window_bytes_uploaded")]
+
+
+class BgzfOpts(ctypes.Structure):
+    _fields_ = [("deflate", DeflateOpts), ("block_size", ctypes.c_uint32)]
+
+
+class BgzfInfo(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("blocks", "data_blocks", "total_out", "error_offset")] + [
+        ("has_eof", ctypes.c_int)]
+
+
+class BgzfStats(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint64) for f in ("range_calls", "ranges", "blocks_decoded", "in_bytes_uploaded",
+                                               "out_bytes_decoded", "out_bytes_returned")]
 
 
 def _load():
@@ -202,6 +217,15 @@ def _load():
         "zt_deflate_raw_indexed": ([vp, sz, P(DeflateOpts), sz, u8pp, P(sz), u8pp, P(sz)], ctypes.c_int),
         "zt_gzip_compress_indexed": ([vp, sz, P(GzipOpts), u8pp, P(sz), P(u32), u8pp, P(sz)], ctypes.c_int),
         "zt_zlib_compress_indexed": ([vp, sz, P(DeflateOpts), u8pp, P(sz), P(u32), u8pp, P(sz)], ctypes.c_int),
+        # include/zt_bgzf.h
+        "zt_bgzf_compress": ([vp, sz, P(BgzfOpts), u8pp, P(sz), u8pp, P(sz)], ctypes.c_int),
+        "zt_bgzf_index": ([vp, sz, u8pp, P(sz), P(BgzfInfo)], ctypes.c_int),
+        "zt_bgzf_decompress": ([vp, sz, u8pp, P(sz), P(BgzfInfo)], ctypes.c_int),
+        "zt_bgzf_read_ranges": ([vp, sz, vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
+                                 P(ctypes.c_int)], ctypes.c_int),
+        "zt_bgzf_read_virtual": ([vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
+                                  P(ctypes.c_int)], ctypes.c_int),
+        "zt_bgzf_stats_read": ([P(BgzfStats), ctypes.c_int], ctypes.c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -262,6 +286,13 @@ DEFLATE_INDEX_SYMBOLS = [
 # every symbol include/zt_checkpoint.h declares (checked by tests/test_ckpt_host.py)
 CKPT_SYMBOLS = [
     "zt_inflate_ckpt_build", "zt_inflate_ckpt_range", "zt_inflate_ckpt_ranges", "zt_ckpt_stats_read",
+]
+
+
+# every symbol include/zt_bgzf.h declares (checked by tests/test_bgzf_host.py)
+BGZF_SYMBOLS = [
+    "zt_bgzf_compress", "zt_bgzf_index", "zt_bgzf_decompress", "zt_bgzf_read_ranges", "zt_bgzf_read_virtual",
+    "zt_bgzf_stats_read",
 ]
 
 
@@ -1062,6 +1093,120 @@ def gunzip_batch_stats():
 
 
 # ---- device-resident helpers (torch tensors as HBM buffers) -----------------------
+# ---- BGZF (include/zt_bgzf.h) -----------------------------------------------------------
+BGZF_BLOCK_MAX = 65280
+
+
+def bgzf_voffset(coffset, uoffset):
+    """The virtual offset of byte `uoffset` of the block at file offset `coffset`."""
+    return (coffset << 16) | uoffset
+
+
+def _bgzf_info(info):
+    return {f: int(getattr(info, f)) for f, _ in BgzfInfo._fields_}
+
+
+def bgzf_compress(data, level=-1, compression_type=2, block_size=0, want_index=False):
+    """zt_bgzf_compress: the BGZF file of `data`; want_index: (file, .gzi bytes)."""
+    b, n = _cbuf(data)
+    o = BgzfOpts(DeflateOpts(compression_type, 0, level), block_size)
+    out, gzi = ctypes.POINTER(ctypes.c_uint8)(), ctypes.POINTER(ctypes.c_uint8)()
+    olen, glen = ctypes.c_size_t(), ctypes.c_size_t()
+    if want_index:
+        _check(lib.zt_bgzf_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(gzi),
+                                    ctypes.byref(glen)))
+        return _take_pair(out, olen, gzi, glen)
+    _check(lib.zt_bgzf_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen), None, None))
+    return _take(out, olen)
+
+
+def bgzf_index(data, return_info=False):
+    """zt_bgzf_index: the file's .gzi from a host walk (no GPU); return_info:
+    (.gzi, info dict).  A malformed file raises ZtError with `.info`."""
+    b, n = _cbuf(data)
+    gzi = ctypes.POINTER(ctypes.c_uint8)()
+    glen = ctypes.c_size_t()
+    info = BgzfInfo()
+    rc = lib.zt_bgzf_index(b, n, ctypes.byref(gzi), ctypes.byref(glen), ctypes.byref(info))
+    if rc != ZT_OK:
+        err = ZtError(rc, lib.zt_last_error_message().decode(errors="replace"))
+        err.info = _bgzf_info(info)
+        raise err
+    blob = ctypes.string_at(gzi, glen.value)
+    lib.zt_free(gzi)
+    return (blob, _bgzf_info(info)) if return_info else blob
+
+
+def bgzf_decompress(data, return_info=False):
+    """zt_bgzf_decompress: the whole file; return_info: (output, info dict).
+    A failure raises ZtError with `.info` (error_offset: the failing block)."""
+    b, n = _cbuf(data)
+    out = ctypes.POINTER(ctypes.c_uint8)()
+    olen = ctypes.c_size_t()
+    info = BgzfInfo()
+    rc = lib.zt_bgzf_decompress(b, n, ctypes.byref(out), ctypes.byref(olen), ctypes.byref(info))
+    if rc != ZT_OK:
+        err = ZtError(rc, lib.zt_last_error_message().decode(errors="replace"))
+        err.info = _bgzf_info(info)
+        raise err
+    res = _take(out, olen)
+    return (res, _bgzf_info(info)) if return_info else res
+
+
+def _bgzf_results(rc, k, outs, olens, st, return_code):
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    msg = lib.zt_last_error_message().decode(errors="replace") if rc != ZT_OK else ""
+    res, first = [], True
+    for i in range(k):
+        m = ""
+        if st[i] != 0:
+            m = msg if first and st[i] == rc else ERRORS.get(st[i], str(st[i]))
+            first = False
+        res.append((BatchStatus(st[i], m), ctypes.string_at(outs[i], olens[i]) if st[i] == 0 else None))
+        if outs[i]:
+            lib.zt_free(outs[i])
+    return (rc, res) if return_code else res
+
+
+def bgzf_read_ranges(data, ranges, gzi=None, return_code=False):
+    """zt_bgzf_read_ranges: [(off, len), ...] by uncompressed offset in one
+    call.  Returns a list of (BatchStatus, bytes) pairs (bytes None for a failed
+    range); return_code: (code, list).  A call that fails before any range is
+    looked at (a bad .gzi, a file that is not BGZF) raises."""
+    b, n = _cbuf(data)
+    gb, gl = _cbuf(gzi) if gzi is not None else (None, 0)
+    k = len(ranges)
+    offs = (ctypes.c_uint64 * k)(*[r[0] for r in ranges])
+    lens = (ctypes.c_uint64 * k)(*[r[1] for r in ranges])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_bgzf_read_ranges(b, n, gb, gl, offs, lens, k, outs, olens, st)
+    return _bgzf_results(rc, k, outs, olens, st, return_code)
+
+
+def bgzf_read_virtual(data, chunks, return_code=False):
+    """zt_bgzf_read_virtual: [(vbeg, vend), ...] virtual-offset chunks in one
+    call; results as bgzf_read_ranges gives them."""
+    b, n = _cbuf(data)
+    k = len(chunks)
+    vb = (ctypes.c_uint64 * k)(*[c[0] for c in chunks])
+    ve = (ctypes.c_uint64 * k)(*[c[1] for c in chunks])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_bgzf_read_virtual(b, n, vb, ve, k, outs, olens, st)
+    return _bgzf_results(rc, k, outs, olens, st, return_code)
+
+
+def bgzf_stats(reset=False):
+    """Work counters of the BGZF read calls (zt_bgzf_stats_read)."""
+    s = BgzfStats()
+    _check(lib.zt_bgzf_stats_read(ctypes.byref(s), 1 if reset else 0))
+    return {f: int(getattr(s, f)) for f, _ in BgzfStats._fields_}
+
+
 def dev_checksums(ptr, n, crc=0, adler=1, stream=None):
     c, a = ctypes.c_uint32(), ctypes.c_uint32()
     _check(lib.zt_dev_checksums(ptr, n, crc, adler, ctypes.byref(c), ctypes.byref(a), stream))
