@@ -125,7 +125,7 @@ static void check_plan(const CkptView &v, const CkptPlan &p, const uint64_t *off
   std::vector<uint8_t> need(v.nunits, 0);
   uint64_t ret = 0;
   for (size_t i = 0; i < count; ++i) {
-    const IdxRange &r = p.ranges[i];
+    const PlannedRange &r = p.ranges[i];
     if (off[i] > v.total_out) {
       CHECK(r.status == ZT_E_ARG && r.span < 0);
       continue;
@@ -242,15 +242,17 @@ static void check_plan(const CkptView &v, const CkptPlan &p, const uint64_t *off
   // entry inside it that has output since; each names its own uploaded window
   uint32_t at = 0;
   std::set<uint32_t> wins_seen;
-  for (size_t g = 0; g < p.segs.size(); ++g) {
-    const CkSeg &sg = p.segs[g];
+  CHECK(p.seg_win.size() == p.segs.size());
+  for (size_t g = 0; g < p.segs.size() && g < p.seg_win.size(); ++g) {
+    const SegJob &sg = p.segs[g];
+    const int32_t win = p.seg_win[g];
     CHECK(sg.first == at && sg.count >= 1);
     const CkEntry &e = v.e[p.units[sg.first].entry];
     if (e.flags & 1) {
-      CHECK(sg.win >= 0 && (size_t)sg.win < p.wins.size() && p.wins[sg.win] == e.win);
+      CHECK(win >= 0 && (size_t)win < p.wins.size() && p.wins[win] == e.win);
       CHECK(wins_seen.insert(e.win).second);
     } else {
-      CHECK(sg.win < 0 && p.units[sg.first].entry == 0);
+      CHECK(win < 0 && p.units[sg.first].entry == 0);
     }
     const uint64_t seg_off = p.chain[sg.first].out_off;
     CHECK(p.chain[sg.first].desc_off % 512 == 0);
@@ -329,7 +331,7 @@ int main() {
         const CkptPlan p = ckpt_plan(v, s.n, o1, l1, 1);
         CHECK(p.spans.size() == 1 && p.segs.size() == 2);
         if (p.segs.size() == 2)
-          CHECK(p.segs[1].win >= 0 && p.wins[p.segs[1].win] == v.e[v.win_units[i]].win &&
+          CHECK(p.seg_win.size() == 2 && p.seg_win[1] >= 0 && p.wins[p.seg_win[1]] == v.e[v.win_units[i]].win &&
                 p.units[p.segs[1].first].entry == v.win_units[i]);
       }
       // random batches: unsorted, overlapping, repeated, some empty, some past the end

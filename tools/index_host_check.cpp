@@ -88,7 +88,7 @@ static void check_plan(const IndexView &v, const RangePlan &p, const uint64_t *o
   // spans: flagged start, in order, not overlapping or touching, inside the index
   uint64_t units = 0, tok = 0;
   for (size_t k = 0; k < p.spans.size(); ++k) {
-    const IdxSpan &s = p.spans[k];
+    const RangeSpan &s = p.spans[k];
     CHECK(s.first <= s.last && s.last < v.nunits);
     CHECK(v.flags[s.first] & 1);
     if (k) CHECK(s.first > p.spans[k - 1].last + 1);
@@ -140,7 +140,7 @@ static void check_plan(const IndexView &v, const RangePlan &p, const uint64_t *o
   // ranges
   uint64_t ret = 0;
   for (size_t i = 0; i < count; ++i) {
-    const IdxRange &r = p.ranges[i];
+    const PlannedRange &r = p.ranges[i];
     CHECK(r.dst % 256 == 0 && r.dst + r.len <= p.dst_total);
     if (i) CHECK(r.dst >= p.ranges[i - 1].dst + (p.ranges[i - 1].len ? p.ranges[i - 1].len : 1));
     if (off[i] > v.total_out) {
@@ -155,7 +155,7 @@ static void check_plan(const IndexView &v, const RangePlan &p, const uint64_t *o
       continue;
     }
     CHECK(r.span >= 0 && (size_t)r.span < p.spans.size());
-    const IdxSpan &s = p.spans[r.span];
+    const RangeSpan &s = p.spans[r.span];
     // the span covers the range: it starts at or before the range's own
     // segment start and ends at or after the unit holding its last byte
     CHECK(v.out_off[s.first] <= r.off);

@@ -22,9 +22,10 @@
 // comes back.  (One wave per block with a history ring, inflate_jobs_dev, was
 // built and measured first: 70.9 ms for 256 MiB against 25.5 ms of
 // zt_gunzip_batch on the same file; it is not kept.)  Range calls gather their
-// pieces with range_gather_kernel (index_api.hip) into one packed buffer: one
-// download.  A failing block is decoded again alone by zt_gunzip for the
-// reference's code and message.
+// pieces with range_gather_kernel (range_call.hip) into one packed buffer: one
+// download, into the slab the other range calls use (range_call.h).  A failing
+// block is decoded again alone by zt_gunzip for the reference's code and
+// message.
 #include <atomic>
 #include <cstring>
 #include <map>
@@ -33,7 +34,7 @@
 
 #include "../../include/zt_bgzf.h"
 #include "bgzf_host.h"
-#include "zt_internal.h"
+#include "range_call.h"
 
 namespace zt {
 
@@ -55,9 +56,6 @@ size_t write_group_blocks() {
 }
 
 // ---- the read side's kernel ------------------------------------------------------
-// a status slot nobody has written
-constexpr int32_t kNotRun = 1;
-
 struct BgzfDevBlock {
   uint64_t cdata_end;  // where its CDATA ends in the uploaded input
   uint32_t isize, crc;
@@ -257,22 +255,11 @@ int decode_blocks_dev(DeviceCtx *c, const uint8_t *in, const BgzfNeed *blocks, s
     for (const Run &r : runs) ZT_TRY(upload(c, static_cast<uint8_t *>(d_in) + r.dev, in + r.file, r.len, s));
   }
   ZT_HIP(hipMemcpyAsync(d_tab, tab.data(), T.upload_bytes, hipMemcpyHostToDevice, s));
-  TokParams tp{};
-  tp.in = static_cast<const uint8_t *>(d_in);
-  tp.n = in_total;
-  tp.order = nullptr;
-  tp.stops = reinterpret_cast<const uint64_t *>(T.jobs);  // never read: nstops = 0
-  tp.nstops = 0;
-  tp.jobs = T.jobs;
-  tp.res = T.res;
-  tp.tokens = static_cast<uint32_t *>(d_tok);
-  tp.count = (uint32_t)nb;
-  tp.simt = tok_simt_env();
-  tp.dbg = nullptr;
-  tp.dump_unit = 0xFFFFFFFFu;
-  tp.dump_once = 0;
-  tp.run_tokens = 1;
-  ZT_TRY(tokenize_units_dev(tp, s));
+  // (stops: never read, nstops = 0)
+  ZT_TRY(tokenize_units_dev(tok_params_planned(static_cast<const uint8_t *>(d_in), in_total,
+                                               reinterpret_cast<const uint64_t *>(T.jobs), 0, T.jobs, T.res,
+                                               static_cast<uint32_t *>(d_tok), (uint32_t)nb),
+                            s));
   BgzfVerify bv;
   bv.blk = T.blk;
   bv.res = T.res;
@@ -373,31 +360,25 @@ int read_requests(const uint8_t *in, std::vector<ReadReq> &req, std::vector<Bgzf
     r.dst = dst_total;
     if (r.status == ZT_OK) dst_total += align_up(r.len ? r.len : 1, 256);  // (>= 1 byte: every pointer distinct)
   }
-  uint8_t *slab = slab_out(dst_total, count, true);
-  if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
-  auto give_up = [&](int rc) {
-    for (size_t i = 0; i < count; ++i) slab_release(slab);
-    for (size_t i = 0; i < count; ++i) out[i] = nullptr, out_len[i] = 0;
-    return rc;
-  };
+  const RangeSlab slab{slab_out(dst_total, count, true), count, out, out_len};
+  if (!slab.base) return set_error(ZT_E_NOMEM, "host allocation failed");
   std::map<size_t, std::pair<int, std::string>> failed;  // block slot -> its own code and message
   if (nb) {  // (nothing to decode: no GPU touched)
     DeviceCtx *c;
-    if (const int rc = get_ctx(&c)) return give_up(rc);
+    if (const int rc = get_ctx(&c)) return slab.give_up(rc);
     std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
     Decoded D;
-    if (const int rc = decode_blocks_dev(c, in, uniq.data(), nb, &D)) return give_up(rc);
+    if (const int rc = decode_blocks_dev(c, in, uniq.data(), nb, &D)) return slab.give_up(rc);
     std::vector<RangeJob> jobs;
     uint64_t tiles = 0;
     for (const ReadReq &r : req) {
       if (r.status != ZT_OK) continue;
       for (const BgzfPiece &p : r.pieces) {
         const size_t slot = bgzf_slot_of(uniq, p.boff);
-        jobs.push_back(RangeJob{D.dec_off[slot] + p.lo, r.dst + p.dst, p.len, (uint32_t)tiles, 0});
-        tiles += (p.len + kGatherTile - 1) / kGatherTile;
+        range_job_add(jobs, &tiles, D.dec_off[slot] + p.lo, r.dst + p.dst, p.len);
       }
     }
-    if (const int rc = gather_download(c, jobs, tiles, D.d_dec, dst_total, slab)) return give_up(rc);
+    if (const int rc = gather_download(c, jobs, tiles, D.d_dec, dst_total, slab.base)) return slab.give_up(rc);
     g_bz.range_calls++;
     g_bz.blocks_decoded += nb;
     g_bz.in_bytes_uploaded += D.in_bytes;
@@ -421,21 +402,10 @@ int read_requests(const uint8_t *in, std::vector<ReadReq> &req, std::vector<Bgzf
       }
     }
   }
-  int rc = ZT_OK;
-  for (size_t i = 0; i < count; ++i) {
-    status[i] = req[i].status;
-    if (req[i].status != ZT_OK) {
-      slab_release(slab);
-      out[i] = nullptr;
-      out_len[i] = 0;
-      if (rc == ZT_OK) rc = set_error(req[i].status, req[i].msg);
-      continue;
-    }
-    out[i] = slab + req[i].dst;
-    out_len[i] = (size_t)req[i].len;
-    g_bz.out_bytes_returned += req[i].len;
-  }
-  return rc;
+  for (size_t i = 0; i < count; ++i) status[i] = req[i].status;
+  return slab.hand_out(
+      status, [&](size_t i) { return req[i].dst; }, [&](size_t i) { return req[i].len; }, g_bz.out_bytes_returned,
+      [&](size_t i) { return set_error(req[i].status, req[i].msg); });
 }
 
 // ---- the write side ---------------------------------------------------------------------
@@ -743,8 +713,7 @@ int zt_bgzf_decompress(const uint8_t *in, size_t n, uint8_t **out, size_t *out_l
           uint64_t tiles = 0;
           for (size_t k = 0; k < nb; ++k) {
             if (!need[k].b.isize) continue;
-            jobs.push_back(RangeJob{D.dec_off[k], w.uoff[k0 + k] - w.uoff[k0], need[k].b.isize, (uint32_t)tiles, 0});
-            tiles += (need[k].b.isize + kGatherTile - 1) / kGatherTile;
+            range_job_add(jobs, &tiles, D.dec_off[k], w.uoff[k0 + k] - w.uoff[k0], need[k].b.isize);
           }
           rc = gather_download(c, jobs, tiles, D.d_dec, glen, h + w.uoff[k0]);
         }
@@ -825,13 +794,12 @@ int zt_bgzf_read_virtual(const uint8_t *in, size_t n, const uint64_t *vbeg, cons
 
 int zt_bgzf_stats_read(zt_bgzf_stats *out, int reset) {
   if (!out) return set_error(ZT_E_ARG, "null output");
-  auto take = [&](std::atomic<uint64_t> &a) { return reset ? a.exchange(0) : a.load(); };
-  out->range_calls = take(g_bz.range_calls);
-  out->ranges = take(g_bz.ranges);
-  out->blocks_decoded = take(g_bz.blocks_decoded);
-  out->in_bytes_uploaded = take(g_bz.in_bytes_uploaded);
-  out->out_bytes_decoded = take(g_bz.out_bytes_decoded);
-  out->out_bytes_returned = take(g_bz.out_bytes_returned);
+  out->range_calls = stat_take(g_bz.range_calls, reset);
+  out->ranges = stat_take(g_bz.ranges, reset);
+  out->blocks_decoded = stat_take(g_bz.blocks_decoded, reset);
+  out->in_bytes_uploaded = stat_take(g_bz.in_bytes_uploaded, reset);
+  out->out_bytes_decoded = stat_take(g_bz.out_bytes_decoded, reset);
+  out->out_bytes_returned = stat_take(g_bz.out_bytes_returned, reset);
   return ZT_OK;
 }
 

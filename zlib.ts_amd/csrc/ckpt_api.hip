@@ -11,8 +11,9 @@
 // A range call plans everything on the host (ckpt_host.h): the blob holds
 // every unit's start state, end state, output offset and token count, so the
 // packed input, the relocated block headers, the units, the chain and its
-// segments are known before anything runs.  One upload carries them and the
-// windows the segments start from; then, without the host waiting in between,
+// segments are known before anything runs.  The driver (range_call.h) carries
+// them and the windows the segments start from up in one upload; then, without
+// the host waiting in between,
 //   1. the checksum kernels give every uploaded window its CRC-32,
 //   2. gen_tokenize_kernel (inflate_gen.hip) decodes the planned units, each an
 //      exact start, one wave per unit, all in parallel,
@@ -20,7 +21,7 @@
 //      to its CRC,
 //   4. expand_kernel + copy_window_kernel (inflate_tok.hip) write the spans to
 //      scratch -- or return at once when anything failed (ChainInfo::ok),
-//   5. range_gather_kernel (index_api.hip) packs the requested sub-ranges,
+//   5. range_gather_kernel (range_call.hip) packs the requested sub-ranges,
 // and one download brings the ranges and every status back.  Candidate
 // search, speculation, link passes and the window chain of the whole-stream
 // path are what the blob replaces.
@@ -30,7 +31,7 @@
 #include <vector>
 
 #include "ckpt_host.h"
-#include "zt_internal.h"
+#include "range_call.h"
 
 namespace zt {
 
@@ -40,8 +41,6 @@ static_assert(CK_BLOCK == GK_BLOCK && CK_HUFF == GK_HUFF && CK_STORED == GK_STOR
 static_assert(kCkWindow == 32768, "a window is the copy kernels' history ring");
 
 namespace {
-
-constexpr int32_t kNotRun = 1;  // a status slot nobody has written (expand / copy returned at once)
 
 // ---- the build's window table ----------------------------------------------------
 // One workgroup per window checkpoint: out[off - 32768, off) into the window's
@@ -130,14 +129,10 @@ __global__ __launch_bounds__(256) void ckpt_verify_kernel(CkVerify P) {
   }
 }
 
-struct CkptCounters {
-  std::atomic<uint64_t> builds{0}, range_calls{0}, ranges{0}, units_tokenized{0}, in_bytes_uploaded{0},
-      out_bytes_decoded{0}, out_bytes_returned{0}, window_bytes_uploaded{0};
+struct CkptCounters : RangeCounters {
+  std::atomic<uint64_t> builds{0}, window_bytes_uploaded{0};
 };
 CkptCounters g_ck;
-
-// ZT_INDEX_TIMING=1: host wall time of a range call's stages on stderr (measurement only)
-#define XT(label) ZT_STAMP("ZT_INDEX_TIMING", "ckpt", label)
 
 int ckpt_error(int status, int detail) {
   if (status == ZT_E_INDEX_MISMATCH) return set_error(status, "checkpoint blob does not match the stream");
@@ -145,121 +140,55 @@ int ckpt_error(int status, int detail) {
   return inflate_error(status, detail);
 }
 
-// the one upload's layout (kRangeIn and its pinned mirror), then the device-only results
-struct CkTables {
-  GenJob *jobs;
-  CkExpect *exp;
-  ChainUnit *chain;
-  SegJob *segs;
-  int32_t *seg_win;
-  RangeJob *rjobs;
-  uint32_t *crc_want;
-  uint64_t *win_off, *win_len;  // checksums_batch_dev reads these on the host: the mirror's only
-  ChainInfo *info;
-  uint8_t *in;
-  uint8_t *wins;
-  size_t upload_bytes;
-  GenResult *res;
-  uint32_t *crc_got;
-  size_t bytes;
-};
-CkTables ckpt_tables(void *base, const CkptPlan &p, size_t njobs) {
-  Carve cv(base);
-  CkTables t;
-  const size_t nu = p.units.size(), nw = p.wins.size();
-  t.jobs = cv.take<GenJob>(nu);
-  t.exp = cv.take<CkExpect>(nu);
-  t.chain = cv.take<ChainUnit>(nu);
-  t.segs = cv.take<SegJob>(p.segs.size());
-  t.seg_win = cv.take<int32_t>(p.segs.size());
-  t.rjobs = cv.take<RangeJob>(njobs);
-  t.crc_want = cv.take<uint32_t>(nw);
-  t.win_off = cv.take<uint64_t>(nw);
-  t.win_len = cv.take<uint64_t>(nw);
-  t.info = cv.take<ChainInfo>(1);
-  t.in = cv.take<uint8_t>(p.in_total + 256);  // + slack: the reader's aligned loads
-  t.wins = cv.take<uint8_t>(nw * kCkWindow);
-  t.upload_bytes = cv.bytes();
-  t.res = cv.take<GenResult>(nu);
-  t.crc_got = cv.take<uint32_t>(2 * nw);
-  t.bytes = cv.bytes();
-  return t;
-}
-// the one download's layout (kRangeOut; the host slab mirrors it)
-struct CkOut {
-  uint8_t *bytes;
-  int32_t *vstatus, *unit_status, *seg_status, *win_status;
-  size_t total;
-};
-CkOut ckpt_out(void *base, const CkptPlan &p) {
-  Carve cv(base);
-  CkOut o;
-  o.bytes = cv.take<uint8_t>(p.dst_total);
-  o.vstatus = cv.take<int32_t>(2 * p.units.size());
-  o.unit_status = cv.take<int32_t>(p.units.size());
-  o.seg_status = cv.take<int32_t>(p.segs.size());
-  o.win_status = cv.take<int32_t>(p.wins.size());
-  o.total = cv.bytes();
-  return o;
-}
-
 // one call's upload is staged whole; a call that asks for more is refused
 constexpr size_t kCkptStageMax = 1u << 30;
 
-int ckpt_ranges_impl(const uint8_t *in, size_t n, const uint8_t *idx, size_t idx_len, const uint64_t *off,
-                     const uint64_t *len, size_t count, uint8_t **out, size_t *out_len, int *status) {
-  CkptView v;
-  if (const char *why = ckpt_validate(idx, idx_len, n, &v))
-    return set_error(ZT_E_INDEX, std::string("invalid checkpoint blob: ") + why);
-  const CkptPlan plan = ckpt_plan(v, n, off, len, count);
-  g_ck.ranges += count;
-  for (size_t i = 0; i < count; ++i) {
-    out[i] = nullptr;
-    out_len[i] = 0;
-    status[i] = plan.ranges[i].status;
-  }
-  const size_t nu = plan.units.size(), ns = plan.segs.size(), nw = plan.wins.size();
-  std::vector<RangeJob> rjobs;
-  uint64_t tiles = 0;
-  for (const IdxRange &r : plan.ranges) {
-    if (r.span < 0) continue;
-    rjobs.push_back(RangeJob{r.src, r.dst, r.len, (uint32_t)tiles, 0});
-    tiles += (r.len + kGatherTile - 1) / kGatherTile;
-  }
-  if (tiles > 0x7FFFFFFFull || nu > 0x7FFFFFFFull) return set_error(ZT_E_ARG, "too many ranges for one call");
-  const CkOut ho_layout = ckpt_out(nullptr, plan);
-  uint8_t *slab = slab_out(nu ? ho_layout.total : plan.dst_total, count, true);
-  if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
-  auto give_up = [&](int rc) {
-    for (size_t i = 0; i < count; ++i) slab_release(slab);
-    for (size_t i = 0; i < count; ++i) out[i] = nullptr, out_len[i] = 0;
-    return rc;
+// what the checkpoint blob hands the range-call driver (range_call.h)
+struct CkptFormat {
+  static constexpr const char *kTag = "ckpt", *kUpload = "hipMemcpyAsync (checkpoint range tables)";
+  const uint8_t *in;
+  const CkptView &v;
+  const CkptPlan &plan;
+  RangeCounters &counters;
+  // in the upload: units | end states | the segments' windows | CRCs | windows
+  // (the packed input holds the block headers, then the spans); device-only:
+  // the unit results and the windows' CRCs as computed
+  struct Tables {
+    GenJob *jobs;
+    CkExpect *exp;
+    int32_t *seg_win;
+    uint32_t *crc_want;
+    uint64_t *win_off, *win_len;  // checksums_batch_dev reads these on the host: the mirror's only
+    uint8_t *wins;
+    GenResult *res;
+    uint32_t *crc_got;
   };
-  int first = ZT_OK, first_detail = 0;
-  if (nu) {  // (nothing to decode: no GPU touched)
-    const CkTables lay = ckpt_tables(nullptr, plan, rjobs.size());
-    if (lay.upload_bytes > kCkptStageMax) return give_up(set_error(ZT_E_ARG, "ranges too large for one call"));
-    DeviceCtx *c;
-    if (const int rc = get_ctx(&c)) return give_up(rc);
-    std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-    hipStream_t s = c->stream;
-    XT("planned");
-    void *d_tab, *h_tab, *d_tok, *d_desc, *d_dec, *d_ro;
-#define RT(call)                                     \
-  do {                                               \
-    if (const int rc_ = (call)) return give_up(rc_); \
-  } while (0)
-    RT(scratch(c, kRangeIn, lay.bytes, &d_tab));
-    RT(pinned(c, lay.upload_bytes, &h_tab, kPinBatch));
-    RT(scratch(c, kTokens, ((size_t)plan.tok_total + 256) * 4, &d_tok));  // + slack: chunked token reads
-    RT(scratch(c, kDeflateOrDesc, ((size_t)plan.desc_total + 1024) * 2, &d_desc));  // + slack: chunked descriptor reads
-    RT(scratch(c, kOut, (size_t)plan.dec_total + 256, &d_dec));
-    RT(scratch(c, kRangeOut, ho_layout.total, &d_ro));
-    const CkTables D = ckpt_tables(d_tab, plan, rjobs.size()), H = ckpt_tables(h_tab, plan, rjobs.size());
-    const CkOut DO = ckpt_out(d_ro, plan);
-    // the one upload: [units | end states | chain | segments | their windows | ranges | CRCs | chain summary |
-    // block headers and packed spans | windows]
-    for (size_t u = 0; u < nu; ++u) {
+  struct Out {
+    int32_t *win_status;
+  };
+  void carve_upload(Carve &cv, Tables *t) const {
+    const size_t nu = plan.units.size(), nw = plan.wins.size();
+    t->jobs = cv.take<GenJob>(nu);
+    t->exp = cv.take<CkExpect>(nu);
+    t->seg_win = cv.take<int32_t>(plan.segs.size());
+    t->crc_want = cv.take<uint32_t>(nw);
+    t->win_off = cv.take<uint64_t>(nw);
+    t->win_len = cv.take<uint64_t>(nw);
+    t->wins = cv.take<uint8_t>(nw * kCkWindow);
+  }
+  void carve_device(Carve &cv, Tables *t) const {
+    t->res = cv.take<GenResult>(plan.units.size());
+    t->crc_got = cv.take<uint32_t>(2 * plan.wins.size());
+  }
+  void carve_out(Carve &cv, Out *o) const { o->win_status = cv.take<int32_t>(plan.wins.size()); }
+  int admit(const RangeTables &lay, bool *staged) const {
+    if (lay.upload_bytes > kCkptStageMax) return set_error(ZT_E_ARG, "ranges too large for one call");
+    *staged = true;
+    return ZT_OK;
+  }
+  const uint8_t *span_src(const CkSpan &sp) const { return in + sp.byte0; }
+  void fill(const RangeTables &T, const Tables &H) const {
+    for (size_t u = 0; u < plan.units.size(); ++u) {
       const CkUnit &j = plan.units[u];
       GenJob g{};
       g.st.pos = j.pos;
@@ -274,128 +203,67 @@ int ckpt_ranges_impl(const uint8_t *in, size_t n, const uint8_t *idx, size_t idx
       H.jobs[u] = g;
       H.exp[u] = CkExpect{j.e_pos, j.e_hdr, j.e_kind, j.e_rem, j.e_bfinal, j.ntok, j.out_len, 0};
     }
-    memcpy(H.chain, plan.chain.data(), nu * sizeof(ChainUnit));
-    for (size_t g = 0; g < ns; ++g) {
-      H.segs[g] = SegJob{plan.segs[g].first, plan.segs[g].count};
-      H.seg_win[g] = plan.segs[g].win;
-    }
-    if (!rjobs.empty()) memcpy(H.rjobs, rjobs.data(), rjobs.size() * sizeof(RangeJob));
-    *H.info = ChainInfo{1, (uint32_t)ns, plan.dec_total, 0, plan.desc_total};
+    memcpy(H.seg_win, plan.seg_win.data(), plan.seg_win.size() * sizeof(int32_t));
     for (const CkHdr &h : plan.hdrs) {
-      memcpy(H.in + h.slot, in + h.src, h.len);
-      memset(H.in + h.slot + h.len, 0, kCkHdrSlot - h.len);
+      memcpy(T.in + h.slot, in + h.src, h.len);
+      memset(T.in + h.slot + h.len, 0, kCkHdrSlot - h.len);
     }
-    for (const CkSpan &sp : plan.spans) copy_to_staging(H.in + sp.in_pos, in + sp.byte0, sp.in_len);
-    for (size_t w = 0; w < nw; ++w) {
+    for (size_t w = 0; w < plan.wins.size(); ++w) {
       copy_to_staging(H.wins + w * kCkWindow, v.wins + (size_t)plan.wins[w] * kCkWinRec, kCkWindow);
       H.crc_want[w] = ckpt_window_crc(v, plan.wins[w]);
       H.win_off[w] = (uint64_t)w * kCkWindow;
       H.win_len[w] = kCkWindow;
     }
-    {
-      const hipError_t e = hipMemcpyAsync(d_tab, h_tab, lay.upload_bytes, hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) return give_up(hip_fail(e, "hipMemcpyAsync (checkpoint range tables)"));
-    }
-    XT("uploaded");
+  }
+  int enqueue(DeviceCtx *c, const RangeTables &D, const Tables &X, const Tables &H, const RangeOut &DO, const Out &DX,
+              uint32_t *d_tok, ResolveParams rp, hipStream_t s) const {
+    const size_t nu = plan.units.size(), nw = plan.wins.size();
     // (the checksum launcher's own small tables go up with blocking copies: it
     // comes first, so that those wait for the upload and for no kernel)
-    if (nw) RT(checksums_batch_dev(c, D.wins, nw, H.win_off, H.win_len, D.crc_got, s));
-    RT(gen_tokenize_exact_dev(D.in, plan.in_total, D.jobs, D.res, static_cast<uint32_t *>(d_tok), (uint32_t)nu, s));
+    if (nw) ZT_TRY(checksums_batch_dev(c, X.wins, nw, H.win_off, H.win_len, X.crc_got, s));
+    ZT_TRY(gen_tokenize_exact_dev(D.in, plan.in_total, X.jobs, X.res, d_tok, (uint32_t)nu, s));
     CkVerify cv;
-    cv.res = D.res;
-    cv.exp = D.exp;
+    cv.res = X.res;
+    cv.exp = X.exp;
     cv.cu = D.chain;
     cv.info = D.info;
-    cv.crc_got = D.crc_got;
-    cv.crc_want = D.crc_want;
+    cv.crc_got = X.crc_got;
+    cv.crc_want = X.crc_want;
     cv.vstatus = DO.vstatus;
     cv.unit_status = DO.unit_status;
     cv.seg_status = DO.seg_status;
-    cv.win_status = DO.win_status;
+    cv.win_status = DX.win_status;
     cv.nunits = (uint32_t)nu;
-    cv.nseg = (uint32_t)ns;
+    cv.nseg = rp.nseg;
     cv.nwin = (uint32_t)nw;
-    const size_t lanes = std::max(nu, std::max(ns, nw));
+    const size_t lanes = std::max(nu, std::max<size_t>(rp.nseg, nw));
     ckpt_verify_kernel<<<(uint32_t)((lanes + 255) / 256), 256, 0, s>>>(cv);
-    if (hipGetLastError() != hipSuccess) return give_up(set_error(ZT_E_HIP, "ckpt_verify_kernel launch failed"));
-    ResolveParams rp;
-    rp.tokens = static_cast<const uint32_t *>(d_tok);
-    rp.units = D.chain;
-    rp.segs = D.segs;
-    rp.out = static_cast<uint8_t *>(d_dec);
-    rp.desc = static_cast<uint16_t *>(d_desc);
-    rp.unit_status = DO.unit_status;
-    rp.seg_status = DO.seg_status;
-    rp.nunits = (uint32_t)nu;
-    rp.nseg = (uint32_t)ns;
+    if (hipGetLastError() != hipSuccess) return set_error(ZT_E_HIP, "ckpt_verify_kernel launch failed");
     rp.marker = 1;  // a segment that is not the stream's first reaches into its window
     rp.in = nullptr;  // (the general tokenizer writes no run tokens)
-    rp.info = D.info;
-    rp.order = nullptr;
-    RT(resolve_segments_window_dev(rp, D.wins, D.seg_win, s));
-    RT(range_gather_dev(D.rjobs, (uint32_t)rjobs.size(), (uint32_t)tiles, static_cast<const uint8_t *>(d_dec), DO.bytes,
-                        D.info, s));
-    XT("launched");
-    // the one download: the packed ranges and every status
-    RT(download(c, slab, d_ro, ho_layout.total, s));
-#undef RT
-    XT("downloaded");
-    g_ck.range_calls++;
-    g_ck.units_tokenized += nu;
-    g_ck.in_bytes_uploaded += plan.in_bytes;
-    g_ck.out_bytes_decoded += plan.dec_bytes;
-    g_ck.window_bytes_uploaded += nw * kCkWindow;
-    const CkOut HO = ckpt_out(slab, plan);
-    // a failure, in stream order: a window's CRC, the tokenizer's status or
-    // the mismatch, then expand's, then copy's
-    std::vector<int32_t> ust(nu, ZT_OK);
-    for (size_t g = 0; g < ns; ++g) {
-      const int32_t w = plan.segs[g].win;
+    return resolve_segments_window_dev(rp, X.wins, X.seg_win, s);
+  }
+  // a window that fails its CRC fails the first unit of its segment
+  void downloaded(const Out &HO, std::vector<int32_t> &ust, int *first) const {
+    g_ck.window_bytes_uploaded += plan.wins.size() * kCkWindow;
+    for (size_t g = 0; g < plan.segs.size(); ++g) {
+      const int32_t w = plan.seg_win[g];
       if (w >= 0 && HO.win_status[w] != ZT_OK) {
         ust[plan.segs[g].first] = ZT_E_INDEX;
-        if (first == ZT_OK) first = ZT_E_INDEX;
-      }
-    }
-    for (size_t u = 0; u < nu; ++u) {
-      if (ust[u] == ZT_OK)
-        ust[u] = HO.vstatus[2 * u] != ZT_OK ? HO.vstatus[2 * u] : HO.unit_status[u] < 0 ? HO.unit_status[u] : ZT_OK;
-      if (ust[u] != ZT_OK && first == ZT_OK) {
-        first = ust[u];
-        first_detail = HO.vstatus[2 * u] != ZT_OK ? HO.vstatus[2 * u + 1] : 0;
-      }
-    }
-    for (size_t g = 0; g < ns && first == ZT_OK; ++g)
-      if (HO.seg_status[g] != ZT_OK) first = HO.seg_status[g] < 0 ? HO.seg_status[g] : ZT_E_INTERNAL;
-    if (first != ZT_OK) {
-      // the decode was abandoned (ChainInfo::ok): every range with bytes
-      // fails, with its own span's first failure where it has one
-      for (size_t i = 0; i < count; ++i) {
-        const IdxRange &r = plan.ranges[i];
-        if (r.span < 0) continue;
-        const CkSpan &sp = plan.spans[r.span];
-        status[i] = first;
-        for (uint32_t k = 0; k <= sp.last - sp.first; ++k)
-          if (ust[sp.unit0 + k] != ZT_OK) {
-            status[i] = ust[sp.unit0 + k];
-            break;
-          }
+        if (*first == ZT_OK) *first = ZT_E_INDEX;
       }
     }
   }
-  int rc = ZT_OK;
-  for (size_t i = 0; i < count; ++i) {
-    if (status[i] != ZT_OK) {
-      slab_release(slab);
-      if (rc == ZT_OK)
-        rc = status[i] == ZT_E_ARG ? set_error(ZT_E_ARG, "range starts past the end of the output")
-                                   : ckpt_error(status[i], status[i] == first ? first_detail : 0);
-      continue;
-    }
-    out[i] = slab + plan.ranges[i].dst;
-    out_len[i] = (size_t)plan.ranges[i].len;
-    g_ck.out_bytes_returned += plan.ranges[i].len;
-  }
-  return rc;
+  int error(int status, int detail) const { return ckpt_error(status, detail); }
+};
+
+int ckpt_ranges_impl(const uint8_t *in, size_t n, const uint8_t *idx, size_t idx_len, const uint64_t *off,
+                     const uint64_t *len, size_t count, uint8_t **out, size_t *out_len, int *status) {
+  CkptView v;
+  if (const char *why = ckpt_validate(idx, idx_len, n, &v))
+    return set_error(ZT_E_INDEX, std::string("invalid checkpoint blob: ") + why);
+  const CkptPlan plan = ckpt_plan(v, n, off, len, count);
+  return range_call(CkptFormat{in, v, plan, g_ck}, count, out, out_len, status);
 }
 
 // the blob of converged entries `e` (windows placed, nwin of them) with its
@@ -589,15 +457,14 @@ int zt_inflate_ckpt_range(const uint8_t *in, size_t n, const uint8_t *idx, size_
 
 int zt_ckpt_stats_read(zt_ckpt_stats *out, int reset) {
   if (!out) return set_error(ZT_E_ARG, "null output");
-  auto take = [&](std::atomic<uint64_t> &a) { return reset ? a.exchange(0) : a.load(); };
-  out->builds = take(g_ck.builds);
-  out->range_calls = take(g_ck.range_calls);
-  out->ranges = take(g_ck.ranges);
-  out->units_tokenized = take(g_ck.units_tokenized);
-  out->in_bytes_uploaded = take(g_ck.in_bytes_uploaded);
-  out->out_bytes_decoded = take(g_ck.out_bytes_decoded);
-  out->out_bytes_returned = take(g_ck.out_bytes_returned);
-  out->window_bytes_uploaded = take(g_ck.window_bytes_uploaded);
+  out->builds = stat_take(g_ck.builds, reset);
+  out->range_calls = stat_take(g_ck.range_calls, reset);
+  out->ranges = stat_take(g_ck.ranges, reset);
+  out->units_tokenized = stat_take(g_ck.units_tokenized, reset);
+  out->in_bytes_uploaded = stat_take(g_ck.in_bytes_uploaded, reset);
+  out->out_bytes_decoded = stat_take(g_ck.out_bytes_decoded, reset);
+  out->out_bytes_returned = stat_take(g_ck.out_bytes_returned, reset);
+  out->window_bytes_uploaded = stat_take(g_ck.window_bytes_uploaded, reset);
   return ZT_OK;
 }
 

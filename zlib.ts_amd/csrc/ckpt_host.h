@@ -188,16 +188,11 @@ inline const char *ckpt_validate(const uint8_t *idx, size_t idx_len, size_t n, C
 inline uint32_t ckpt_window_crc(const CkptView &v, uint32_t w) { return idx_get32(v.wins + w * kCkWinRec + kCkWindow); }
 
 // ---- the planner ---------------------------------------------------------------
-// Units [first, last] of the blob decoded as one piece: `first` is entry 0 or a
-// window entry, `last` holds the last byte any of its ranges asks for.
-struct CkSpan {
-  uint32_t first = 0, last = 0;
-  uint32_t unit0 = 0;    // its first planned unit
-  uint64_t byte0 = 0;    // first compressed byte in `in`: pos[first] / 8
-  uint64_t in_pos = 0;   // where that byte lies in the packed input (64-aligned)
-  uint64_t in_len = 0;   // compressed bytes, up to the byte holding pos[last + 1]
-  uint64_t out_pos = 0;  // where out_off[first] lies in the decode buffer (256-aligned)
-  uint64_t out_len = 0;
+// (the ranges, the span base and the totals: range_plan.h.)  `first` is entry 0
+// or a window entry; in_pos is where byte0 lies in the packed input, in_len
+// runs up to the byte holding pos[last + 1].
+struct CkSpan : RangeSpan {
+  uint64_t byte0 = 0;  // first compressed byte in `in`: pos[first] / 8
 };
 // A dynamic block header that lies before its span, packed once per call.
 struct CkHdr {
@@ -218,78 +213,21 @@ struct CkUnit {
   uint32_t ntok, out_len;
   uint32_t entry;                // its entry in the blob
 };
-// A copy segment: chain units [first, first + count), its history ring
-// starting as uploaded window `win` (-1: the stream start, no history).
-struct CkSeg {
-  uint32_t first = 0, count = 0;
-  int32_t win = -1;
-};
-struct CkptPlan {
-  std::vector<IdxRange> ranges;
+// (in_total: header slots, then spans)
+struct CkptPlan : RangePlanCore {
   std::vector<CkSpan> spans;
   std::vector<CkHdr> hdrs;        // ascending by hdr
   std::vector<CkUnit> units;
-  std::vector<ChainUnit> chain;
-  std::vector<CkSeg> segs;
+  // per copy segment: its history ring starts as uploaded window seg_win[g]
+  // (-1: the stream start, no history)
+  std::vector<int32_t> seg_win;
   std::vector<uint32_t> wins;     // blob window of each uploaded window
-  uint64_t in_total = 0;    // packed input bytes: header slots, then spans
-  uint64_t in_bytes = 0;    // of them, compressed bytes (the rest is alignment)
-  uint64_t dec_total = 0;   // decode buffer bytes
-  uint64_t dec_bytes = 0;
-  uint64_t desc_total = 0;
-  uint64_t tok_total = 0;
-  uint64_t dst_total = 0;
-  uint64_t ret_bytes = 0;
 };
 
 inline CkptPlan ckpt_plan(const CkptView &v, size_t n, const uint64_t *off, const uint64_t *len, size_t count) {
   CkptPlan p;
-  p.ranges.resize(count);
-  std::vector<CkSpan> want;
   auto out_of = [&](uint32_t k) { return v.e[k].out_off; };
-  for (size_t i = 0; i < count; ++i) {
-    IdxRange &r = p.ranges[i];
-    r.off = off[i];
-    if (r.off > v.total_out) {
-      r.status = ZT_E_ARG;
-      continue;
-    }
-    r.len = std::min<uint64_t>(len[i], v.total_out - r.off);
-    if (r.len == 0) continue;
-    // first: the last of entry 0 and the window entries with out_off <= off
-    size_t lo = 0, hi = v.win_units.size();
-    while (hi - lo > 1) {
-      const size_t mid = (lo + hi) / 2;
-      if (out_of(v.win_units[mid]) <= r.off)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    // last: the unit that holds byte off + len - 1 (the last entry with out_off <= it; never the sentinel)
-    const uint64_t e = r.off + r.len - 1;
-    size_t a = 0, b = v.nunits;  // out_off[a] <= e < out_off[b]
-    while (b - a > 1) {
-      const size_t mid = (a + b) / 2;
-      if (out_of((uint32_t)mid) <= e)
-        a = mid;
-      else
-        b = mid;
-    }
-    CkSpan s;
-    s.first = v.win_units[lo];
-    s.last = (uint32_t)a;
-    want.push_back(s);
-  }
-  // spans that overlap or touch become one: no unit is decoded twice
-  std::sort(want.begin(), want.end(), [](const CkSpan &a, const CkSpan &b) {
-    return a.first != b.first ? a.first < b.first : a.last < b.last;
-  });
-  for (const CkSpan &s : want) {
-    if (!p.spans.empty() && s.first <= p.spans.back().last + 1)
-      p.spans.back().last = std::max(p.spans.back().last, s.last);
-    else
-      p.spans.push_back(s);
-  }
+  p.spans = range_spans<CkSpan>(v.total_out, v.win_units, v.nunits, out_of, off, len, count, &p.ranges);
   // the headers that lie before the span of a unit that names them, once each
   std::vector<uint64_t> hs;
   for (CkSpan &s : p.spans) {
@@ -326,23 +264,9 @@ inline CkptPlan ckpt_plan(const CkptView &v, size_t n, const uint64_t *off, cons
       const size_t i = (size_t)(std::lower_bound(hs.begin(), hs.end(), h) - hs.begin());
       return p.hdrs[i].slot * 8 + (h & 7);
     };
-    uint64_t seg_start = 0, desc_seg = 0;
+    SegLayout lay(p.chain, p.segs, p.desc_total);
     for (uint32_t u = s.first; u <= s.last; ++u) {
       const CkEntry &e = v.e[u], &nx = v.e[u + 1];
-      const uint64_t o = e.out_off - out_of(s.first);
-      // a segment starts with the span and at every later window entry that has output since the previous start
-      if (u == s.first || ((e.flags & 1u) && o != seg_start)) {
-        p.desc_total = align_up(p.desc_total, 512);
-        desc_seg = p.desc_total;
-        seg_start = o;
-        CkSeg g;
-        g.first = (uint32_t)p.chain.size();
-        if (e.flags & 1u) {
-          g.win = (int32_t)p.wins.size();
-          p.wins.push_back(e.win);
-        }
-        p.segs.push_back(g);
-      }
       CkUnit j{};
       j.entry = u;
       j.pos = reloc(e.pos);
@@ -361,33 +285,19 @@ inline CkptPlan ckpt_plan(const CkptView &v, size_t n, const uint64_t *off, cons
       j.tok_off = p.tok_total;
       j.tok_cap = e.ntok;
       p.tok_total += align_up((uint64_t)e.ntok + 1, 64);
-      p.chain.push_back(ChainUnit{j.tok_off, s.out_pos + o, s.out_pos + seg_start, desc_seg + (o - seg_start), e.ntok,
-                                  j.out_len});
-      p.segs.back().count++;
+      // a segment that starts at a window entry starts from that window
+      if (lay.add(j.tok_off, s.out_pos + (e.out_off - out_of(s.first)), e.ntok, j.out_len, e.flags & 1u)) {
+        p.seg_win.push_back((e.flags & 1u) ? (int32_t)p.wins.size() : -1);
+        if (e.flags & 1u) p.wins.push_back(e.win);
+      }
       p.units.push_back(j);
-      p.desc_total = desc_seg + (o + j.out_len - seg_start);
     }
     p.in_total += s.in_len;
     p.in_bytes += s.in_len;
     p.dec_total += s.out_len;
     p.dec_bytes += s.out_len;
   }
-  for (IdxRange &r : p.ranges) {
-    r.dst = p.dst_total;
-    p.dst_total += align_up(r.len ? r.len : 1, 256);
-    if (r.status != ZT_OK || r.len == 0) continue;
-    p.ret_bytes += r.len;
-    size_t lo = 0, hi = p.spans.size();
-    while (hi - lo > 1) {
-      const size_t mid = (lo + hi) / 2;
-      if (out_of(p.spans[mid].first) <= r.off)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    r.span = (int32_t)lo;
-    r.src = p.spans[lo].out_pos + (r.off - out_of(p.spans[lo].first));
-  }
+  range_place(p.spans, out_of, &p);
   return p;
 }
 

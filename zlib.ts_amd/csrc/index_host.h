@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/zt_index.h"
-#include "inflate_chain.h"
+#include "range_plan.h"
 
 namespace zt {
 
@@ -142,102 +142,30 @@ inline const char *index_validate(const uint8_t *idx, size_t idx_len, size_t n, 
 }
 
 // ---- the planner ---------------------------------------------------------------
-// One range of a call, clamped.
-struct IdxRange {
-  uint64_t off = 0, len = 0;  // len clamped to total_out - off
-  int32_t status = ZT_OK;     // ZT_E_ARG: off > total_out
-  int32_t span = -1;          // the merged span that decodes it (-1: empty, nothing to decode)
-  uint64_t src = 0;           // its first byte in the decode buffer
-  uint64_t dst = 0;           // its place in the packed output (256-aligned; an empty range reserves 256 bytes)
-};
-// Units [first, last] of the index, decoded as one piece: `first` is a segment
-// start, `last` holds the last byte any of its ranges asks for.
-struct IdxSpan {
-  uint32_t first = 0, last = 0;
-  uint32_t unit0 = 0;     // its first planned unit (jobs / chain index)
-  uint64_t in_pos = 0;    // where in_off[first] lies in the packed input (64-aligned)
-  uint64_t in_len = 0;    // compressed bytes: in_off[last + 1] - in_off[first]
-  uint64_t out_pos = 0;   // where out_off[first] lies in the decode buffer (256-aligned)
-  uint64_t out_len = 0;   // out_off[last + 1] - out_off[first]
-};
-struct RangePlan {
-  std::vector<IdxRange> ranges;
-  std::vector<IdxSpan> spans;
+// (the ranges, the spans and the totals: range_plan.h.  A span's `first` is a
+// segment start; in_pos is where in_off[first] lies in the packed input and
+// in_len = in_off[last + 1] - in_off[first].)
+struct RangePlan : RangePlanCore {
+  std::vector<RangeSpan> spans;
   // per planned unit (all spans, in stream order)
   std::vector<uint64_t> stops;   // packed position where the unit ends (= the next unit's start): sorted
   std::vector<TokJob> jobs;
-  std::vector<ChainUnit> chain;
-  std::vector<SegJob> segs;
   uint32_t final_unit = 0xFFFFFFFFu;  // the planned unit that is the stream's last (ends at BFINAL), if planned
-  uint64_t in_total = 0;    // packed input bytes
-  uint64_t in_bytes = 0;    // of them, compressed bytes (the rest is alignment)
-  uint64_t dec_total = 0;   // decode buffer bytes
-  uint64_t dec_bytes = 0;   // of them, decoded bytes
-  uint64_t desc_total = 0;  // descriptors
-  uint64_t tok_total = 0;   // tokens
-  uint64_t dst_total = 0;   // packed output bytes
-  uint64_t ret_bytes = 0;   // sum of the clamped lengths
 };
 
 inline RangePlan index_plan(const IndexView &v, const uint64_t *off, const uint64_t *len, size_t count) {
   RangePlan p;
-  p.ranges.resize(count);
-  std::vector<IdxSpan> want;
-  for (size_t i = 0; i < count; ++i) {
-    IdxRange &r = p.ranges[i];
-    r.off = off[i];
-    if (r.off > v.total_out) {
-      r.status = ZT_E_ARG;
-      continue;
-    }
-    r.len = std::min<uint64_t>(len[i], v.total_out - r.off);
-    if (r.len == 0) continue;
-    // first: the last segment start with out_off <= off
-    size_t lo = 0, hi = v.seg_units.size();  // seg_units[0] = 0 has out_off 0 <= off
-    while (hi - lo > 1) {
-      const size_t mid = (lo + hi) / 2;
-      if (v.out_off[v.seg_units[mid]] <= r.off)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    // last: the unit that holds byte off + len - 1 (the last entry with out_off <= it; < total_out,
-    // so never the sentinel)
-    const uint64_t e = r.off + r.len - 1;
-    const size_t last = (size_t)(std::upper_bound(v.out_off.begin(), v.out_off.end(), e) - v.out_off.begin()) - 1;
-    IdxSpan s;
-    s.first = v.seg_units[lo];
-    s.last = (uint32_t)last;
-    want.push_back(s);
-  }
-  // spans that overlap or touch become one: no unit is decoded twice
-  std::sort(want.begin(), want.end(), [](const IdxSpan &a, const IdxSpan &b) {
-    return a.first != b.first ? a.first < b.first : a.last < b.last;
-  });
-  for (const IdxSpan &s : want) {
-    if (!p.spans.empty() && s.first <= p.spans.back().last + 1)
-      p.spans.back().last = std::max(p.spans.back().last, s.last);
-    else
-      p.spans.push_back(s);
-  }
+  auto out_of = [&](uint32_t k) { return v.out_off[k]; };
+  p.spans = range_spans<RangeSpan>(v.total_out, v.seg_units, v.nunits, out_of, off, len, count, &p.ranges);
   // the tables of every span's units
-  for (IdxSpan &s : p.spans) {
+  for (RangeSpan &s : p.spans) {
     s.unit0 = (uint32_t)p.jobs.size();
     s.in_pos = p.in_total = align_up(p.in_total, 64);
     s.in_len = v.in_off[s.last + 1] - v.in_off[s.first];
     s.out_pos = p.dec_total = align_up(p.dec_total, 256);
     s.out_len = v.out_off[s.last + 1] - v.out_off[s.first];
-    uint64_t seg_start = 0, desc_seg = 0;  // of the current segment: output offset in the span, descriptors
+    SegLayout lay(p.chain, p.segs, p.desc_total);
     for (uint32_t u = s.first; u <= s.last; ++u) {
-      const uint64_t o = v.out_off[u] - v.out_off[s.first];  // output offset in the span
-      // a segment starts with the span and at every later segment start that
-      // has output since the previous one (seg_chain_host's rule)
-      if (u == s.first || ((v.flags[u] & 1) && o != seg_start)) {
-        p.desc_total = align_up(p.desc_total, 512);
-        desc_seg = p.desc_total;
-        seg_start = o;
-        p.segs.push_back(SegJob{(uint32_t)p.chain.size(), 0});
-      }
       TokJob j;
       j.start = s.in_pos + (v.in_off[u] - v.in_off[s.first]);
       j.tok_off = p.tok_total;
@@ -245,39 +173,19 @@ inline RangePlan index_plan(const IndexView &v, const uint64_t *off, const uint6
       j.tok_cap = idx_tok_slot(v.ntok[u], ol64);
       j.stop_first = (uint32_t)p.stops.size();
       j.end = s.in_pos + s.in_len;
-      const uint32_t ol = (uint32_t)ol64;  // (validated: fits its tokens, < 2^32)
-      p.chain.push_back(ChainUnit{j.tok_off, s.out_pos + o, s.out_pos + seg_start, desc_seg + (o - seg_start),
-                                  v.ntok[u], ol});
-      p.segs.back().count++;
+      // (validated: the unit's output fits its tokens, < 2^32)
+      lay.add(j.tok_off, s.out_pos + (v.out_off[u] - v.out_off[s.first]), v.ntok[u], (uint32_t)ol64, v.flags[u] & 1);
       p.stops.push_back(s.in_pos + (v.in_off[u + 1] - v.in_off[s.first]));
       if (u + 1 == v.nunits) p.final_unit = (uint32_t)p.jobs.size();
       p.jobs.push_back(j);
       p.tok_total += j.tok_cap;
-      p.desc_total = desc_seg + (o + ol - seg_start);
     }
     p.in_total += s.in_len;
     p.in_bytes += s.in_len;
     p.dec_total += s.out_len;
     p.dec_bytes += s.out_len;
   }
-  // every range's place in its span and in the packed output
-  for (IdxRange &r : p.ranges) {
-    r.dst = p.dst_total;
-    p.dst_total += align_up(r.len ? r.len : 1, 256);
-    if (r.status != ZT_OK || r.len == 0) continue;
-    p.ret_bytes += r.len;
-    // the span that holds byte `off`: the last one whose first byte is at or before it
-    size_t lo = 0, hi = p.spans.size();
-    while (hi - lo > 1) {
-      const size_t mid = (lo + hi) / 2;
-      if (v.out_off[p.spans[mid].first] <= r.off)
-        lo = mid;
-      else
-        hi = mid;
-    }
-    r.span = (int32_t)lo;
-    r.src = p.spans[lo].out_pos + (r.off - v.out_off[p.spans[lo].first]);
-  }
+  range_place(p.spans, out_of, &p);
   return p;
 }
 

@@ -3,7 +3,9 @@
 // resolve kernels read, and the two host functions that turn the first into
 // the second -- seg_chain_host for one large stream (inflate_seg.hip; its
 // device twin is chain_kernel there) and batch_chain_host for a batch of
-// small streams (inflate_api.cpp).  No device code and no HIP types:
+// small streams (inflate_api.cpp) -- and SegLayout, the segment rule that
+// seg_chain_host and the range planners (index_host.h, ckpt_host.h) lay their
+// chains out by.  No device code and no HIP types:
 // tools/inflate_chain_check.cpp runs it under ASan / UBSan.
 #pragma once
 #include <cstddef>
@@ -59,6 +61,39 @@ struct ChainInfo {
 // v rounded up to a multiple of a (every host file's one rounding function)
 inline uint64_t align_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a; }
 
+// The segment layout of a run of units that follow each other in one output
+// buffer, appended to a chain unit by unit: a segment starts with the first
+// unit and at every later start entry that has output since the previous
+// start, and its descriptors start 512-aligned.
+// (A start entry right after another -- the empty stored blocks of a restart
+// marker -- leaves the segment before it empty: that one simply starts here
+// instead.  Empty copy waves would sit between the full ones in the launch,
+// and the workgroup -> XCD round robin would then give half of the XCDs every
+// 1 MiB segment: two rounds of copy waves.)
+struct SegLayout {
+  std::vector<ChainUnit> &chain;
+  std::vector<SegJob> &segs;
+  uint64_t &desc_total;
+  bool open = false;
+  uint64_t seg_start = 0, desc_seg = 0;  // of the current segment: output offset, descriptors
+  SegLayout(std::vector<ChainUnit> &c, std::vector<SegJob> &s, uint64_t &d) : chain(c), segs(s), desc_total(d) {}
+  // out_off: the unit's place in the buffer; returns true when the unit opened a segment
+  bool add(uint64_t tok_off, uint64_t out_off, uint32_t ntok, uint32_t out_len, bool start_entry) {
+    const bool opens = !open || (start_entry && out_off != seg_start);
+    if (opens) {
+      desc_total = align_up(desc_total, 512);
+      desc_seg = desc_total;
+      seg_start = out_off;
+      segs.push_back(SegJob{(uint32_t)chain.size(), 0});
+      open = true;
+    }
+    chain.push_back(ChainUnit{tok_off, out_off, seg_start, desc_seg + (out_off - seg_start), ntok, out_len});
+    segs.back().count++;
+    desc_total = desc_seg + (out_off + out_len - seg_start);
+    return opens;
+  }
+};
+
 // What the host makes of one stream's unit tables.
 struct ChainPlan {
   enum Outcome {
@@ -85,7 +120,8 @@ struct ChainPlan {
 inline ChainPlan seg_chain_host(const TokResult *res, const uint8_t *restart, const uint64_t *tok_off, size_t units) {
   ChainPlan p;
   char msg[160];
-  uint64_t total = 0, seg_start = 0, desc_total = 0, desc_seg = 0;
+  uint64_t total = 0, desc_total = 0;
+  SegLayout lay(p.chain, p.segs, desc_total);
   size_t u = 0;
   for (;;) {
     const TokResult &r = res[u];
@@ -105,24 +141,9 @@ inline ChainPlan seg_chain_host(const TokResult *res, const uint8_t *restart, co
       p.why = msg;
       return p;
     }
-    // (a restart point right after another -- the empty stored blocks of a
-    // restart marker -- leaves the segment before it empty: that one simply
-    // starts here instead.  Empty copy waves would sit between the full ones
-    // in the launch, and the workgroup -> XCD round robin would then give
-    // half of the XCDs every 1 MiB segment: two rounds of copy waves.)
-    const bool seg_start_here = u == 0 || restart[u - 1];
-    if (p.segs.empty() || (seg_start_here && total != seg_start)) {
-      desc_total = align_up(desc_total, 512);
-      desc_seg = desc_total;
-      seg_start = total;
-      p.segs.push_back(SegJob{(uint32_t)p.chain.size(), 0});
-    }
-    p.chain.push_back(ChainUnit{tok_off[u], total, seg_start, desc_seg + (total - seg_start), r.ntok,
-                                (uint32_t)r.out_len});
+    lay.add(tok_off[u], total, r.ntok, (uint32_t)r.out_len, u == 0 || restart[u - 1]);
     p.on_chain.push_back((uint32_t)u);
-    p.segs.back().count++;
     total += r.out_len;
-    desc_total = desc_seg + (total - seg_start);
     if (r.stop_idx < 0) break;
     const size_t nx = (size_t)r.stop_idx + 1;
     if (nx <= u || nx >= units) {

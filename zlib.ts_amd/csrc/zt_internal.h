@@ -1,5 +1,6 @@
 // zt_internal.h -- shared host/device helpers for libzt (not installed).
 #pragma once
+#include <atomic>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -90,10 +91,11 @@ enum ScratchSlot : int {
   kDict = 29,       // a preset dictionary (zt_dict.h: deflate history | inflate window | the whole dictionary);
                     // the holder may call the batch deflate / inflate launchers
   kIndexPack = 30,  // index build (inflate_seg.hip): on-chain unit ids | packed index entries; after resolve, inside the call
-  kRangeIn = 31,    // range inflate (index_api.hip): stops | TokJob | chain | segments | ranges | ChainInfo |
-                    // packed input (one upload), then TokResult; whole call (it also takes kTokens, kDeflateOrDesc and kOut)
-  kRangeOut = 32,   // range inflate: packed ranges | statuses, one download; whole call
-                    // (31, 32: the checkpoint range decode of ckpt_api.hip uses them the same way, never inside the other)
+  kRangeIn = 31,    // a range call (range_call.h: the index and checkpoint formats; BGZF's decode_blocks_dev): chain |
+                    // segments | ranges | ChainInfo | the format's tables | packed input (one upload), then the
+                    // format's device-only results; whole call (it also takes kTokens, kDeflateOrDesc and kOut)
+  kRangeOut = 32,   // a range call: packed ranges | statuses (| the format's), one download; whole call
+                    // (31, 32: one range call at a time, never inside another)
   kCkptWin = 33,    // checkpoint build (ckpt_api.hip): window offsets | window records; after the general decode, inside the call
   kScratchSlots
 };
@@ -174,6 +176,9 @@ void host_stamp(const char *tag, const char *label);  // "[tag] label  <now_ms()
     static const bool on_ = getenv(env) != nullptr; \
     if (on_) ::zt::host_stamp(tag, label);          \
   } while (0)
+
+// a *_stats_read counter: its value, zeroed when `reset`
+inline uint64_t stat_take(std::atomic<uint64_t> &a, int reset) { return reset ? a.exchange(0) : a.load(); }
 
 // Records the begin / end event of interval k (0 or 1) when timing is on.
 int timing_begin(DeviceCtx *c, hipStream_t s, int k = 0);
@@ -704,18 +709,48 @@ inline int tok_simt_env() {
   static const char *e = getenv("ZT_TOK_SIMT");
   return e ? atoi(e) != 0 : 1;
 }
+// `count` units planned on the host (the range calls): every unit's job is
+// uploaded, no launch order, no debug words, stored runs as run tokens
+inline TokParams tok_params_planned(const uint8_t *in, uint64_t n, const uint64_t *stops, uint64_t nstops,
+                                    const TokJob *jobs, TokResult *res, uint32_t *tokens, uint32_t count) {
+  TokParams tp;
+  tp.in = in;
+  tp.n = n;
+  tp.order = nullptr;
+  tp.stops = stops;
+  tp.nstops = nstops;
+  tp.jobs = jobs;
+  tp.res = res;
+  tp.tokens = tokens;
+  tp.count = count;
+  tp.simt = tok_simt_env();
+  tp.dbg = nullptr;
+  tp.dump_unit = 0xFFFFFFFFu;
+  tp.dump_once = 0;
+  tp.run_tokens = 1;
+  return tp;
+}
 int tokenize_units_dev(const TokParams &p, hipStream_t s);
 int resolve_segments_dev(const ResolveParams &p, hipStream_t s);
 int expand_units_dev(const ResolveParams &p, hipStream_t s);
-// One requested range with bytes (index_api.hip, ckpt_api.hip): dec[src .. src
-// + len) -> out[dst ..], dst 256-aligned; its tiles are workgroups [tile0,
-// tile0 + ceil(len / kGatherTile)) of range_gather_kernel, which does nothing
-// unless info->ok.
+// One requested range with bytes (the range calls: range_call.h, bgzf_api.hip):
+// dec[src .. src + len) -> out[dst ..]; its tiles are workgroups [tile0, tile0
+// + ceil(len / kGatherTile)) of range_gather_kernel (range_call.hip), which
+// does nothing unless info->ok.
 struct RangeJob {
   uint64_t src, dst, len;
   uint32_t tile0, pad;
 };
 constexpr uint32_t kGatherTile = 32768;
+// the next job of a call's list; *tiles: the workgroups so far (the caller
+// holds them to 0x7FFFFFFF before the launch)
+inline void range_job_add(std::vector<RangeJob> &jobs, uint64_t *tiles, uint64_t src, uint64_t dst, uint64_t len) {
+  jobs.push_back(RangeJob{src, dst, len, (uint32_t)*tiles, 0});
+  *tiles += (len + kGatherTile - 1) / kGatherTile;
+}
+// a status slot nobody has written (the verify kernels of the range calls set
+// it; expand / copy returned at once)
+constexpr int32_t kNotRun = 1;
 int range_gather_dev(const RangeJob *d_jobs, uint32_t njobs, uint32_t tiles, const uint8_t *d_dec, uint8_t *d_out,
                      const ChainInfo *d_info, hipStream_t s);
 // expand_kernel (p.marker = 1), then copy_window_kernel: segment g's 32 KiB
