@@ -68,7 +68,8 @@ static int download_result(DeviceCtx *c, const uint8_t *d_out, size_t ol, bool p
 
 static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<size_t> &in_off, const size_t *n,
                            const size_t *index, size_t count, uint8_t **out, size_t *out_len,
-                           std::vector<InfResult> &res, std::vector<size_t> &failed, uint32_t *sums = nullptr) {
+                           std::vector<InfResult> &res, std::vector<size_t> &failed, uint32_t *sums = nullptr,
+                           const DevSink *sink = nullptr) {
   hipStream_t s = c->stream;
   std::vector<size_t> ids;
   for (size_t i = 0; i < count; ++i) {
@@ -176,15 +177,23 @@ static int batch_two_phase(DeviceCtx *c, const uint8_t *d_in, const std::vector<
     // the slab comes from the host output pool -- registered once its items
     // are freed -- and a registered one takes the DMA directly (the staged
     // download and a copy-out into a fresh slab cost ~7 ms per 256 MiB, C2)
-    uint8_t *slab = slab_out(out_total, done.size(), true);
-    if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
-    if (const int rc = download(c, slab, d_out, out_total, s)) {
-      for (size_t q = 0; q < done.size(); ++q) slab_release(slab);
-      return rc;
+    // (a device sink takes them from d_out where they lie: nothing comes back)
+    uint8_t *slab = nullptr;
+    if (sink) {
+      std::vector<SinkPiece> pieces;
+      for (const size_t j : done) pieces.push_back(SinkPiece{ids[who[j]], chain[j].out_off, chain[j].out_len});
+      ZT_TRY(sink->put(static_cast<const uint8_t *>(d_out), pieces, s));
+    } else {
+      slab = slab_out(out_total, done.size(), true);
+      if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
+      if (const int rc = download(c, slab, d_out, out_total, s)) {
+        for (size_t q = 0; q < done.size(); ++q) slab_release(slab);
+        return rc;
+      }
     }
     for (const size_t j : done) {
       const size_t k = who[j], i = ids[k];
-      out[i] = slab + chain[j].out_off;
+      out[i] = sink ? nullptr : slab + chain[j].out_off;
       out_len[i] = chain[j].out_len;
       InfResult &r = res[i];
       r = InfResult{};
@@ -212,6 +221,7 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
                              size_t *end_ip, int *status, const uint8_t *d_hist = nullptr, uint32_t hist_len = 0,
                              const BatchExtras *extras = nullptr) {
   uint32_t *sums = extras ? extras->sums : nullptr;
+  const DevSink *sink = extras ? extras->sink : nullptr;
   std::vector<size_t> cap(count);
   for (size_t i = 0; i < count; ++i) {
     // first guess (4x the stream's bytes from its start); exact sizes are
@@ -234,8 +244,9 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
   // stream for whatever it leaves (ZT_BATCH_ONEWAVE=1 forces the latter)
   static const bool onewave = getenv("ZT_BATCH_ONEWAVE") != nullptr;
   // (with extras, batches of any size: members of any length come through here)
-  if (!strict && (count >= 8 || extras) && !onewave && !hist_len) {
-    ZT_TRY(batch_two_phase(c, (const uint8_t *)d_in, in_off, n, index, count, out, out_len, res, todo, sums));
+  // (a sink alone does not: a small device-resident batch takes the host call's route)
+  if (!strict && (count >= 8 || (extras && (!sink || sums))) && !onewave && !hist_len) {
+    ZT_TRY(batch_two_phase(c, (const uint8_t *)d_in, in_off, n, index, count, out, out_len, res, todo, sums, sink));
     std::sort(todo.begin(), todo.end());
     if (extras && extras->speculative) {
       std::vector<size_t> keep;
@@ -298,12 +309,19 @@ static int inflate_dev_batch(DeviceCtx *c, const void *d_in, const std::vector<s
       out[i] = nullptr;
       out_len[i] = 0;
       if (r[k].status == ZT_OK) {
-        out[i] = (uint8_t *)malloc(r[k].out_len ? r[k].out_len : 1);
-        if (!out[i]) return set_error(ZT_E_NOMEM, "host allocation failed");
+        if (!sink) {
+          out[i] = (uint8_t *)malloc(r[k].out_len ? r[k].out_len : 1);
+          if (!out[i]) return set_error(ZT_E_NOMEM, "host allocation failed");
+        }
         out_len[i] = r[k].out_len;
         done.push_back(k);
-        if (out_off[k] + r[k].out_len > span) span = out_off[k] + r[k].out_len;
+        if (!sink && out_off[k] + r[k].out_len > span) span = out_off[k] + r[k].out_len;
       }
+    }
+    if (sink && !done.empty()) {  // (the device sink: the finished outputs leave d_out by kernel, before the rerun reuses it)
+      std::vector<SinkPiece> pieces;
+      for (const size_t k : done) pieces.push_back(SinkPiece{todo[k], out_off[k], r[k].out_len});
+      ZT_TRY(sink->put(static_cast<const uint8_t *>(d_out), pieces, c->stream));
     }
     // (sums: over the finished outputs' device copies, beside the download)
     std::vector<uint32_t> hsums;

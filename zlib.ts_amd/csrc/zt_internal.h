@@ -15,6 +15,7 @@
 #include "../../include/zt.h"
 #include "batch_plan.h"
 #include "deflate_index_host.h"
+#include "dev_batch_plan.h"
 #include "dict_host.h"
 #include "inflate_chain.h"
 
@@ -97,6 +98,8 @@ enum ScratchSlot : int {
   kRangeOut = 32,   // a range call: packed ranges | statuses (| the format's), one download; whole call
                     // (31, 32: one range call at a time, never inside another)
   kCkptWin = 33,    // checkpoint build (ckpt_api.hip): window offsets | window records; after the general decode, inside the call
+  kDevBatch = 34,   // device-resident batch calls (dev_batch_api.cpp): the copy and patch job tables of one launch;
+                    // the holder calls the batch deflate / inflate and checksum launchers (none asks for it)
   kScratchSlots
 };
 // Pinned host staging (DeviceCtx::h_pinned, pinned()).
@@ -586,7 +589,28 @@ struct BatchExtras {
   // cannot finish is not decoded again by one wave; it gets ZT_E_INPUT_BROKEN,
   // which is then no more than "failed" (not the reference's status)
   const uint8_t *speculative = nullptr;
+  // The device sink (zt_inflate_dev_batch, dev_batch_api.cpp): finished
+  // outputs are not downloaded.  Both decoder routes hand every batch of
+  // finished streams to sink->put while their bytes still lie in the decode
+  // buffer; out[i] stays null and out_len[i] is the stream's length.  With a
+  // sink and no sums, batches of fewer than 8 streams go to the one-wave
+  // decoder as the host call's do.
+  const struct DevSink *sink = nullptr;
 };
+// a finished stream: `len` bytes at d_base + off belong to item `item`
+struct SinkPiece {
+  size_t item;
+  uint64_t off, len;
+};
+struct DevSink {
+  // queues the copies on s (ordered behind the decode); the pieces' bytes may
+  // be overwritten by whatever s runs next
+  std::function<int(const uint8_t *d_base, const std::vector<SinkPiece> &pieces, hipStream_t s)> put;
+};
+// dev_batch.hip: the copy jobs' tiles (dev_batch_plan.h) and the patch jobs,
+// tables on the device
+int dev_copy_dev(const DevCopyJob *d_jobs, uint32_t njobs, uint64_t tiles, hipStream_t s);
+int dev_patch_dev(const DevPatchJob *d_jobs, uint32_t njobs, const uint32_t *d_sums, hipStream_t s);
 // Decode `count` device-resident streams (stream i at d_in + in_off[i],
 // n[i] bytes, from index[i]); outputs are malloc'd.
 int inflate_batch_dev_streams(DeviceCtx *c, const void *d_in, const std::vector<size_t> &in_off, const size_t *n,

@@ -226,6 +226,13 @@ def _load():
         "zt_bgzf_read_virtual": ([vp, sz, P(ctypes.c_uint64), P(ctypes.c_uint64), sz, u8pp, P(sz),
                                   P(ctypes.c_int)], ctypes.c_int),
         "zt_bgzf_stats_read": ([P(BgzfStats), ctypes.c_int], ctypes.c_int),
+        # include/zt_dev_batch.h
+        "zt_deflate_dev_batch": ([P(vp), P(sz), sz, P(DeflateOpts), ctypes.c_int, P(vp), P(sz), P(sz),
+                                  P(ctypes.c_int), vp], ctypes.c_int),
+        "zt_deflate_dev_batch_bound": ([sz, ctypes.c_int, ctypes.c_int], sz),
+        "zt_inflate_dev_batch": ([P(vp), P(sz), P(sz), sz, P(vp), P(sz), P(sz), P(sz), P(ctypes.c_int), P(u32),
+                                  P(u32), vp], ctypes.c_int),
+        "zt_debug_dev_batch_times": ([ctypes.c_int, P(ctypes.c_double)], ctypes.c_int),  # debug (dev_batch_api.cpp)
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -293,6 +300,12 @@ CKPT_SYMBOLS = [
 BGZF_SYMBOLS = [
     "zt_bgzf_compress", "zt_bgzf_index", "zt_bgzf_decompress", "zt_bgzf_read_ranges", "zt_bgzf_read_virtual",
     "zt_bgzf_stats_read",
+]
+
+
+# every symbol include/zt_dev_batch.h declares (checked by tests/test_dev_batch_host.py)
+DEV_BATCH_SYMBOLS = [
+    "zt_deflate_dev_batch", "zt_deflate_dev_batch_bound", "zt_inflate_dev_batch",
 ]
 
 
@@ -1252,6 +1265,139 @@ class InflatePlan:
 
 def deflate_bound(n):
     return lib.zt_deflate_bound(n)
+
+
+# ---- include/zt_dev_batch.h: batches of device buffers, by pointer ----------------
+DEV_BATCH_FORMATS = {"raw": 0, "zlib": 1, "gzip": 2}
+
+
+def deflate_dev_batch_bound(n, compression_type=2, format="raw", level=-1):
+    """Upper bound of one item's output (level 0 writes stored blocks, as type 0)."""
+    return lib.zt_deflate_dev_batch_bound(n, 0 if level == 0 else compression_type,
+                                          DEV_BATCH_FORMATS.get(format, format))
+
+
+def _ptr_array(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*[int(p) or None for p in ptrs])
+
+
+def deflate_dev_batch(ptrs, sizes, out_ptrs, out_caps, format="raw", level=-1, compression_type=2, stream=None):
+    """Device buffers (ptrs[i], sizes[i]) deflated into (out_ptrs[i], out_caps[i]).
+    Returns (out_lens, statuses); an item that does not fit has ZT_E_ARG and the
+    length it needs.  Raises only when the call fails as a whole."""
+    k = len(ptrs)
+    olens, st = (ctypes.c_size_t * k)(), (ctypes.c_int * k)()
+    opts = DeflateOpts(compression_type, 0, level)
+    rc = lib.zt_deflate_dev_batch(_ptr_array(ptrs), (ctypes.c_size_t * k)(*sizes), k, ctypes.byref(opts),
+                                  DEV_BATCH_FORMATS.get(format, format), _ptr_array(out_ptrs),
+                                  (ctypes.c_size_t * k)(*out_caps), olens, st, stream)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    return list(olens), list(st)
+
+
+def inflate_dev_batch(ptrs, sizes, out_ptrs, out_caps=None, index=None, checksums=False, stream=None):
+    """Raw DEFLATE streams in device buffers decoded into device buffers.
+    out_ptrs None: sizes only.  Returns (out_lens, end_ips, statuses), with
+    checksums=True also (crcs, adlers).  Per-item failures are statuses, with
+    the first one's message in zt_last_error_message as zt_inflate_raw_batch
+    leaves it; raises only when the call fails as a whole."""
+    k = len(ptrs)
+    olens, ips, st = (ctypes.c_size_t * k)(), (ctypes.c_size_t * k)(), (ctypes.c_int * k)()
+    crcs = (ctypes.c_uint32 * k)() if checksums else None
+    adlers = (ctypes.c_uint32 * k)() if checksums else None
+    rc = lib.zt_inflate_dev_batch(_ptr_array(ptrs), (ctypes.c_size_t * k)(*sizes),
+                                  (ctypes.c_size_t * k)(*index) if index is not None else None, k,
+                                  _ptr_array(out_ptrs) if out_ptrs is not None else None,
+                                  (ctypes.c_size_t * k)(*out_caps) if out_ptrs is not None else None,
+                                  olens, ips, st, crcs, adlers, stream)
+    if rc != ZT_OK and all(s == 0 for s in st):
+        _check(rc)
+    res = (list(olens), list(ips), list(st))
+    return res + (list(crcs), list(adlers)) if checksums else res
+
+
+def debug_dev_batch_times(enable):
+    """(gather ms, scatter ms) by HIP events since the last call, cleared; the
+    timing is on for the following calls when `enable` (measurement only)."""
+    v = (ctypes.c_double * 2)()
+    _check(lib.zt_debug_dev_batch_times(1 if enable else 0, v))
+    return v[0], v[1]
+
+
+def _torch_stream(tensors, stream):
+    """The stream handle to pass for a list of cuda tensors: the given one, else
+    torch's current stream.  NULL names the library's own stream, which does
+    not wait for torch's default stream, so with that one current it is
+    synchronised first (the calls wait for their own work before returning)."""
+    import torch
+
+    if stream is not None:
+        return stream
+    s = torch.cuda.current_stream(tensors[0].device if tensors else None)
+    if not s.cuda_stream:
+        s.synchronize()
+        return None
+    return s.cuda_stream
+
+
+def _check_tensors(tensors):
+    import torch
+
+    for t in tensors:
+        if t.dtype != torch.uint8 or not t.is_cuda or t.dim() != 1 or (t.numel() > 1 and t.stride(0) != 1):
+            raise ValueError("expected one-dimensional contiguous uint8 cuda tensors")
+
+
+def deflate_tensors(tensors, format="raw", level=-1, compression_type=2, stream=None):
+    """Every uint8 cuda tensor of the list deflated on the device; returns a list
+    of uint8 cuda tensors, views into one output tensor sized by the bound."""
+    import torch
+
+    _check_tensors(tensors)
+    if not tensors:
+        return []
+    sizes = [t.numel() for t in tensors]
+    caps = [deflate_dev_batch_bound(n, compression_type, format, level) for n in sizes]
+    offs, tot = [], 0
+    for c in caps:
+        offs.append(tot)
+        tot += (c + 15) & ~15
+    s = _torch_stream(tensors, stream)
+    out = torch.empty(tot, dtype=torch.uint8, device=tensors[0].device)
+    base = out.data_ptr()
+    lens, st = deflate_dev_batch([t.data_ptr() for t in tensors], sizes, [base + o for o in offs], caps,
+                                 format=format, level=level, compression_type=compression_type, stream=s)
+    if any(st):
+        _check(st[[bool(x) for x in st].index(True)])
+    return [out[o:o + n] for o, n in zip(offs, lens)]
+
+
+def inflate_tensors(tensors, out_sizes=None, stream=None):
+    """Every raw DEFLATE stream of the list (uint8 cuda tensors) decoded on the
+    device; returns a list of uint8 cuda tensors, views into one output tensor.
+    out_sizes None: the sizes come from a sizes-only call first."""
+    import torch
+
+    _check_tensors(tensors)
+    if not tensors:
+        return []
+    ptrs, sizes = [t.data_ptr() for t in tensors], [t.numel() for t in tensors]
+    s = _torch_stream(tensors, stream)
+    if out_sizes is None:
+        out_sizes, _, st = inflate_dev_batch(ptrs, sizes, None, stream=s)
+        if any(st):
+            _check(st[[bool(x) for x in st].index(True)])
+    offs, tot = [], 0
+    for c in out_sizes:
+        offs.append(tot)
+        tot += (c + 15) & ~15
+    out = torch.empty(max(tot, 1), dtype=torch.uint8, device=tensors[0].device)
+    base = out.data_ptr()
+    lens, _, st = inflate_dev_batch(ptrs, sizes, [base + o for o in offs], list(out_sizes), stream=s)
+    if any(st):
+        _check(st[[bool(x) for x in st].index(True)])
+    return [out[o:o + n] for o, n in zip(offs, lens)]
 
 
 GEN_KINDS = {"xorshift32": 0, "wordsalad": 1, "structured": 2, "mixed": 3}
