@@ -93,6 +93,45 @@ guarded("gunzip_batch", lambda: decoded(zt.gunzip_batch(gz + zl[:3])))
 guarded("zlib_decompress_batch", lambda: decoded(zt.zlib_decompress_batch(zl + gz[:3], verify=True)))
 guarded("zlib_decompress_batch_d", lambda: decoded(zt.zlib_decompress_batch(zl_d + zl, verify=True, dictionary=dic)))
 guarded("zlib_decompress_batch_nd", lambda: decoded(zt.zlib_decompress_batch(zl_d[:5] + zl)))
+
+# ---- every writer of a member's frame (csrc/member_frame.h): the single-buffer
+# calls, BGZF and the device-resident batch
+text = items[9]  # 70000 bytes of words
+guarded("gzip_compress", lambda: list(zt.gzip_compress(text, name=b"n", hcrc=True, mtime=7)))
+guarded("gzip_compress_indexed", lambda: list(zt.gzip_compress_indexed(text, name=b"n", hcrc=True, mtime=7)))
+guarded("zlib_compress", lambda: list(zt.zlib_compress(text)))
+guarded("zlib_compress_indexed", lambda: list(zt.zlib_compress_indexed(text)))
+guarded("zlib_compress_dict", lambda: list(zt.zlib_compress(text, dictionary=dic)))
+for bs in (4096, 0):
+    for level in (0, 6):
+        guarded(f"bgzf_compress_bs{bs}_L{level}", lambda: [
+            p for n in (0, 1, 4096, 4097, 70000)
+            for p in zt.bgzf_compress(text[:n], level=level, block_size=bs, want_index=True)])
+
+
+def dev_batch(fmt, ct):
+    """sizes 0 .. 70000 through zt_deflate_dev_batch, item 3 with too little room:
+    per item its status, the length it reports and the bytes it wrote"""
+    import torch
+    srcs = [text[:n] for n in (0, 1, 65535, 65536, 70000)]
+    pieces = [s + bytes(-len(s) % 256 + 256) for s in srcs]  # (each from a 256-byte boundary)
+    offs = [sum(len(p) for p in pieces[:k]) for k in range(len(srcs))]
+    tin = torch.frombuffer(bytearray(b"".join(pieces)), dtype=torch.uint8).cuda()
+    caps = [zt.deflate_dev_batch_bound(len(s), ct, fmt) for s in srcs]
+    caps[3] = 100
+    room = max(caps) + 256
+    out = torch.full((room * len(srcs),), 0xA5, dtype=torch.uint8, device="cuda")
+    lens, st = zt.deflate_dev_batch([tin.data_ptr() + o for o in offs], [len(s) for s in srcs],
+                                    [out.data_ptr() + k * room for k in range(len(srcs))], caps, format=fmt,
+                                    compression_type=ct)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().tobytes()
+    return [(st[k], lens[k], got[k * room:k * room + (lens[k] if st[k] == 0 else room)]) for k in range(len(srcs))]
+
+
+for fmt in ("raw", "zlib", "gzip"):
+    for ct in (0, 1, 2):
+        guarded(f"deflate_dev_batch_{fmt}_ct{ct}", lambda: dev_batch(fmt, ct))
 if MODE == "dev1":
     sys.stdout.flush()
     env = dict(os.environ, ZT_ALIAS_DEVICES="3")

@@ -245,14 +245,15 @@ static void test_groups() {
 // ---- sizes ----------------------------------------------------------------------
 static void test_sizes() {
   const size_t ns[] = {0, 1, 65535, 65536, 131070, 131071};
-  const size_t blocks[] = {0, 1, 1, 2, 2, 3};  // by hand: stored blocks of <= 65535 bytes
+  // by hand: stored blocks of <= 65535 bytes (the empty input is one empty block)
+  const size_t blocks[] = {1, 1, 1, 2, 2, 3};
   for (int k = 0; k < 6; ++k) {
-    size_t slow = 0;
-    for (size_t left = ns[k]; left;) {  // block by block
+    size_t slow = 0, left = ns[k];
+    do {  // block by block
       const size_t l = std::min<size_t>(left, 65535);
       slow += 5 + l;
       left -= l;
-    }
+    } while (left);
     CHECK(stored_len(ns[k]) == slow);
     CHECK(stored_len(ns[k]) == ns[k] + 5 * blocks[k]);
     CHECK(deflate_out_bound(0, ns[k], 999) == slow + 16);

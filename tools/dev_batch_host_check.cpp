@@ -2,12 +2,8 @@
 // batch calls (zlib.ts_amd/csrc/dev_batch_plan.h) without a device: the copy
 // jobs and their tile table, the patch jobs, the stored-block job list, the
 // output bound, the groups, the capacity masking and the tile limit, each
-// against a slow restatement.  The job tables are run by a host model of
-// dev_copy_kernel / dev_patch_kernel (dev_batch.hip) that follows the kernel's
-// index arithmetic access by access: every 16-byte load must be aligned and
-// hold at least one byte of the job's source, bytes of such a word outside
-// the source read as garbage (so a result that depended on them would differ),
-// and every store must lie inside the job's destination.  Meant to be built
+// against a slow restatement.  The job tables are run by the host model of
+// dev_copy_kernel / dev_patch_kernel in tools/dev_batch_model.h.  Meant to be built
 // with a sanitizer and run on its own (tests/test_dev_batch_host.py):
 //
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -22,18 +18,7 @@
 #include <vector>
 
 #include "../zlib.ts_amd/csrc/deflate_index_host.h"  // restart_after
-#include "../zlib.ts_amd/csrc/dev_batch_plan.h"
-
-using namespace zt;
-
-static int fails = 0;
-#define CHECK(c)                                                      \
-  do {                                                                \
-    if (!(c)) {                                                       \
-      if (fails < 20) fprintf(stderr, "line %d: %s\n", __LINE__, #c); \
-      ++fails;                                                        \
-    }                                                                 \
-  } while (0)
+#include "dev_batch_model.h"
 
 typedef std::vector<uint8_t> Bytes;
 
@@ -45,89 +30,11 @@ static uint32_t rnd() {
   return rng_state;
 }
 
-// ---- the kernels' host model ------------------------------------------------------
-static uint8_t load_byte(const DevCopyJob &j, uint64_t addr) {
-  CHECK(addr >= j.src && addr < j.src + j.len);
-  return *reinterpret_cast<const uint8_t *>(addr);
-}
-static void store_byte(const DevCopyJob &j, uint64_t addr, uint8_t v) {
-  CHECK(addr >= j.dst && addr < j.dst + j.len + j.zero);
-  if (addr >= j.dst && addr < j.dst + j.len + j.zero) *reinterpret_cast<uint8_t *>(addr) = v;
-}
-// an aligned 16-byte load: must hold a byte of the source; the bytes outside
-// the source are garbage
-static void load16(const DevCopyJob &j, uint64_t addr, uint8_t w[16]) {
-  CHECK((addr & 15) == 0);
-  CHECK(addr + 16 > j.src && addr < j.src + j.len);
-  for (int k = 0; k < 16; ++k) {
-    const uint64_t a = addr + k;
-    w[k] = (a >= j.src && a < j.src + j.len) ? *reinterpret_cast<const uint8_t *>(a) : (uint8_t)(0xE0 | k);
-  }
-}
-// one workgroup of dev_copy_kernel (all its threads, in turn)
-static void model_tile(const std::vector<DevCopyJob> &jobs, uint32_t tile) {
-  const DevCopyJob j = jobs[dev_copy_find(jobs, tile)];
-  const uint64_t o0 = (uint64_t)(tile - j.tile0) * kDevTile;
-  if (o0 >= j.len) return;
-  const bool last_tile = j.len - o0 <= kDevTile;
-  uint32_t n = (uint32_t)(last_tile ? j.len - o0 : kDevTile);
-  uint64_t s = j.src + o0, d = j.dst + o0;
-  if (last_tile)
-    for (uint32_t i = 0; i < j.zero; ++i) store_byte(j, d + n + i, 0);
-  const uint32_t to16 = (uint32_t)((16 - (d & 15)) & 15);
-  const uint32_t lead = to16 < n ? to16 : n;
-  for (uint32_t i = 0; i < lead; ++i) store_byte(j, d + i, load_byte(j, s + i));
-  s += lead;
-  d += lead;
-  n -= lead;
-  const uint32_t body = n & ~15u;
-  const uint32_t sh = (uint32_t)(s & 15);
-  for (uint32_t i = 0; i < body; i += 16) {
-    uint8_t w[32];
-    load16(j, s - sh + i, w);
-    if (sh)
-      load16(j, s - sh + i + 16, w + 16);
-    else
-      memcpy(w + 16, w, 16);
-    CHECK(((d + i) & 15) == 0);  // a 16-byte store
-    for (uint32_t k = 0; k < 16; ++k) store_byte(j, d + i + k, w[sh + k]);
-  }
-  for (uint32_t i = body; i < n; ++i) store_byte(j, d + i, load_byte(j, s + i));
-}
-static void model_copy(const DevCopyPlan &cp) {
-  uint64_t tiles = 0;
-  for (const DevCopyJob &j : cp.jobs) {
-    CHECK(j.len > 0 && j.tile0 == tiles);
-    tiles += (j.len + kDevTile - 1) / kDevTile;
-  }
-  CHECK(tiles == cp.tiles);
-  for (uint64_t t = 0; t < cp.tiles; ++t) model_tile(cp.jobs, (uint32_t)t);
-}
-static void model_patch(const std::vector<DevPatchJob> &pj, const uint32_t *sums) {
-  for (const DevPatchJob &j : pj) {
-    uint8_t *d = reinterpret_cast<uint8_t *>(j.dst);
-    if (j.kind == kPatchGzipTrailer) {
-      CHECK(j.len == 8);
-      const uint32_t crc = sums[2 * j.sum], isize = (uint32_t)j.value;
-      for (int k = 0; k < 4; ++k) d[k] = (uint8_t)(crc >> (8 * k));
-      for (int k = 0; k < 4; ++k) d[4 + k] = (uint8_t)(isize >> (8 * k));
-    } else if (j.kind == kPatchZlibTrailer) {
-      CHECK(j.len == 4);
-      const uint32_t ad = sums[2 * j.sum + 1];
-      for (int k = 0; k < 4; ++k) d[k] = (uint8_t)(ad >> (24 - 8 * k));
-    } else {
-      CHECK(j.kind == kPatchBytes && j.len <= 8);
-      for (uint32_t k = 0; k < j.len && k < 8; ++k) d[k] = (uint8_t)(j.value >> (8 * k));
-    }
-  }
-}
-
 static Bytes filler(size_t n) {
   Bytes b(n);
   for (size_t i = 0; i < n; ++i) b[i] = (uint8_t)(rnd() >> 8);
   return b;
 }
-static uint64_t addr(const uint8_t *p) { return reinterpret_cast<uint64_t>(p); }
 
 // ---- slow restatements ---------------------------------------------------------------
 // stored blocks as the host batch call writes them (batch_api.cpp)
@@ -190,20 +97,20 @@ static void check_stored_and_frames() {
         // (the input as a view at an odd offset; its own allocation of n bytes for the bounds)
         Bytes in(backing.begin() + mis, backing.begin() + mis + n);
         const Bytes body = slow_stored(in);
-        CHECK(body.size() == dev_stored_len(n));
+        CHECK(body.size() == stored_len(n));
         const uint32_t sums[4] = {0xAABBCCDDu, 0x11223344u, 0xDEADBEEFu, 0x01020304u};
         const Bytes want = slow_frame(fmt, 0, body, sums[2], sums[3], (uint32_t)n);
-        CHECK(want.size() == dev_batch_bound(n, 0, fmt));
+        CHECK(want.size() == dev_batch_bound(n, 0, (MemberKind)fmt));
         Bytes out(want.size() + mis, 0x5A);  // exactly the room: ASan guards the rest
-        uint8_t prefix[10];
-        const uint32_t plen = dev_prefix(fmt, 0, prefix), tl = dev_trailer_len(fmt);
-        CHECK(plen == dev_prefix_len(fmt) && plen + body.size() + tl == want.size());
+        const MemberFrame fr = frame_of((MemberKind)fmt, 0);
+        const uint32_t plen = fr.prefix_len(), tl = fr.trailer_len();
+        CHECK(plen == (fmt == kFmtGzip ? 10u : fmt == kFmtZlib ? 2u : 0u) && plen + body.size() + tl == want.size());
         DevCopyPlan cp;
         std::vector<DevPatchJob> pj;
         const uint64_t dst = addr(out.data()) + mis;
-        dev_patch_prefix(pj, dst, prefix, plen);
+        dev_patch_bytes(pj, dst, fr.prefix.data(), plen);
         CHECK(dev_stored_jobs(addr(in.data()), n, dst + plen, cp, pj));
-        dev_patch_trailer(pj, fmt, dst + plen + body.size(), n, 1);
+        dev_patch_trailer(pj, fr.kind, dst + plen + body.size(), n, 1);
         model_copy(cp);
         model_patch(pj, sums);
         CHECK(memcmp(out.data() + mis, want.data(), want.size()) == 0);
@@ -211,8 +118,8 @@ static void check_stored_and_frames() {
       }
   // zlib's header for every compression type is a multiple of 31
   for (int ct = 0; ct <= 2; ++ct) {
-    uint8_t p[10];
-    CHECK(dev_prefix(kFmtZlib, ct, p) == 2 && p[0] == 0x78 && ((p[0] << 8) + p[1]) % 31 == 0 && (p[1] >> 6) == ct);
+    const std::vector<uint8_t> p = frame_of(kFmtZlib, ct).prefix;
+    CHECK(p.size() == 2 && p[0] == 0x78 && ((p[0] << 8) + p[1]) % 31 == 0 && (p[1] >> 6) == ct);
   }
 }
 

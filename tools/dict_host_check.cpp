@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../zlib.ts_amd/csrc/dict_host.h"
+#include "../zlib.ts_amd/csrc/member_frame.h"  // frame_zlib_dict: the FDICT header's writer
 
 using namespace zt;
 
@@ -69,8 +70,8 @@ int main() {
     // ---- the FDICT header ----
     const uint32_t id = adler32(dict.data(), n);
     for (uint32_t flevel = 0; flevel < 4; ++flevel) {
-      std::vector<uint8_t> hd(6);
-      zlib_dict_header(0x78, flevel, id, hd.data());
+      const std::vector<uint8_t> hd = frame_zlib_dict(flevel, id).prefix;
+      CHECK(hd.size() == 6);
       CHECK(hd[0] == 0x78 && (hd[1] & 0x20) && (hd[1] >> 6) == flevel && ((hd[0] << 8) + hd[1]) % 31 == 0);
       CHECK(((uint32_t)hd[2] << 24 | (uint32_t)hd[3] << 16 | (uint32_t)hd[4] << 8 | hd[5]) == id);
       // parsed back, whole and at every truncation (0..5 bytes) and offset

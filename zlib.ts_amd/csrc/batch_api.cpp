@@ -52,27 +52,15 @@ struct StageTimes {
 };
 
 // fills out[i] (malloc'd: prefix | stream | trailer) for item i
-struct Framing {
-  enum Kind { RAW, GZIP, ZLIB } kind;
-  std::vector<uint8_t> prefix;
-  size_t trailer;
-};
-
 // (dst: the item's place in a batch slab, or null for its own allocation)
-int frame_item(const Framing &fr, size_t n_in, const uint8_t *body, size_t blen, uint32_t crc, uint32_t adler,
+int frame_item(const MemberFrame &fr, size_t n_in, const uint8_t *body, size_t blen, uint32_t crc, uint32_t adler,
                uint8_t **out, size_t *out_len, uint8_t *dst = nullptr) {
-  const size_t total = fr.prefix.size() + blen + fr.trailer;
+  const size_t total = fr.prefix.size() + blen + fr.trailer_len();
   uint8_t *h = dst ? dst : host_out(total);
   if (!h) return set_error(ZT_E_NOMEM, "host allocation failed");
   if (!fr.prefix.empty()) memcpy(h, fr.prefix.data(), fr.prefix.size());
   if (blen) memcpy(h + fr.prefix.size(), body, blen);
-  uint8_t *t = h + fr.prefix.size() + blen;
-  if (fr.kind == Framing::GZIP) {  // CRC-32, ISIZE (src/GZip.ts:179-185)
-    for (int k = 0; k < 4; ++k) t[k] = (crc >> (8 * k)) & 0xFF;
-    for (int k = 0; k < 4; ++k) t[4 + k] = ((uint32_t)n_in >> (8 * k)) & 0xFF;
-  } else if (fr.kind == Framing::ZLIB) {  // Adler-32 big-endian (src/Deflate.ts:95)
-    for (int k = 0; k < 4; ++k) t[k] = (adler >> (24 - 8 * k)) & 0xFF;
-  }
+  put_trailer(h + fr.prefix.size() + blen, fr.kind, crc, adler, (uint32_t)n_in);
   *out = h;
   *out_len = total;
   return ZT_OK;
@@ -80,12 +68,12 @@ int frame_item(const Framing &fr, size_t n_in, const uint8_t *body, size_t blen,
 
 // items [k0, k0 + nb) framed into one slab (slab_out): their offsets, and
 // the slab (null when it cannot be allocated)
-uint8_t *frame_slab(const Framing &fr, const uint64_t *oo, size_t nb, std::vector<size_t> &soff) {
+uint8_t *frame_slab(const MemberFrame &fr, const uint64_t *oo, size_t nb, std::vector<size_t> &soff) {
   soff.resize(nb);
   size_t tot = 0;
   for (size_t j = 0; j < nb; ++j) {
     soff[j] = tot;
-    tot += slab_stride(fr.prefix.size(), oo[j + 1] - oo[j], fr.trailer);
+    tot += slab_stride(fr.prefix.size(), oo[j + 1] - oo[j], fr.trailer_len());
   }
   return slab_out(tot, nb);
 }
@@ -101,12 +89,12 @@ uint8_t *frame_slab(const Framing &fr, const uint64_t *oo, size_t nb, std::vecto
 constexpr uint64_t kGroupMin = 256ull << 20;
 
 int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &work,
-                  const PackLayout &L, const std::vector<uint64_t> &len, int ct, int lv, const Framing &fr,
+                  const PackLayout &L, const std::vector<uint64_t> &len, int ct, int lv, const MemberFrame &fr,
                   uint8_t **out, size_t *out_len, StageTimes &tm, const DictHist *dh) {
   const size_t m = work.size();
   const std::vector<size_t> &off = L.off;
   const uint64_t padded = L.total;
-  const bool sums = fr.kind != Framing::RAW;
+  const bool sums = fr.kind != kFmtRaw;
   // groups [gk[g], gk[g + 1]) of items
   // tuning hook: ZT_BATCH_GROUPS = groups per share (default 6)
   static const int ng_env = getenv("ZT_BATCH_GROUPS") ? atoi(getenv("ZT_BATCH_GROUPS")) : 0;
@@ -163,16 +151,13 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const
     const uint64_t b = gbeg(g);
     std::vector<uint64_t> ro(nb), rl(len.begin() + k0, len.begin() + k0 + nb);
     for (size_t j = 0; j < nb; ++j) ro[j] = off[k0 + j] - b;
+    uint32_t *gsums = sums ? (uint32_t *)d_sums + 2 * k0 : nullptr;
+    ZT_TRY(deflate_members_dev(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), ct, lv,
+                               (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, dh, gsums, pipe.landed(g)));
     if (sums) {
-      ZT_HIP(hipStreamWaitEvent(c->aux, pipe.landed(g), 0));
-      ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), (uint32_t *)d_sums + 2 * k0,
-                                 c->aux));
-      ZT_HIP(hipMemcpyAsync(hsums.data() + 2 * k0, (uint32_t *)d_sums + 2 * k0, 8 * nb, hipMemcpyDeviceToHost,
-                            c->aux));
+      ZT_HIP(hipMemcpyAsync(hsums.data() + 2 * k0, gsums, 8 * nb, hipMemcpyDeviceToHost, c->aux));
+      ZT_HIP(hipStreamSynchronize(c->aux));
     }
-    ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in + b, nb, ro.data(), rl.data(), ct, lv,
-                                 (uint8_t *)d_out + ooff[g], &oo[k0 + g], d_scr, ss, c->stream, dh));
-    if (sums) ZT_HIP(hipStreamSynchronize(c->aux));
     return ZT_OK;
   };
   auto dn_stage = [&](size_t g) -> int {
@@ -202,15 +187,16 @@ int batch_grouped(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const
 
 // one device's share: items `ids` of the batch (for_each_device: c is locked)
 int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, const std::vector<size_t> &ids, int ct,
-                    int lv, const Framing &fr, uint8_t **out, size_t *out_len, const HostDict &hd) {
-  const bool sums = fr.kind != Framing::RAW;
+                    int lv, const MemberFrame &fr, uint8_t **out, size_t *out_len, const HostDict &hd) {
+  const bool sums = fr.kind != kFmtRaw;
   // empty inputs: a final empty stored block, as the one-buffer calls write
   // (deflate.hip) -- no device work
   std::vector<size_t> work;
   for (size_t i : ids) {
     if (n[i] == 0) {
-      static const uint8_t empty_stored[5] = {0x01, 0x00, 0x00, 0xFF, 0xFF};
-      ZT_TRY(frame_item(fr, 0, empty_stored, 5, 0, 1, &out[i], &out_len[i]));
+      uint8_t empty_stored[5];
+      stored_write(nullptr, 0, empty_stored);
+      ZT_TRY(frame_item(fr, 0, empty_stored, sizeof empty_stored, 0, 1, &out[i], &out_len[i]));
     } else {
       work.push_back(i);
     }
@@ -259,16 +245,19 @@ int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, con
   tm.groups = 1;
   // checksums on the second stream, over the same device bytes
   std::vector<uint32_t> hsums(2 * m, 0);
-  void *d_sums = nullptr;
+  void *d_sums = nullptr, *d_out = nullptr, *d_scr = nullptr;
+  size_t ss = 0;
   AuxWait aux_wait{c->aux};
-  if (sums) {
-    ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
-    ZT_HIP(hipEventRecord(c->aux_ev, c->stream));
-    ZT_HIP(hipStreamWaitEvent(c->aux, c->aux_ev, 0));
-    ZT_TRY(checksums_batch_dev(c, (const uint8_t *)d_in, m, off.data(), len.data(), (uint32_t *)d_sums, c->aux));
-    ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * m, hipMemcpyDeviceToHost, c->aux));
+  if (sums) ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
+  if (ct != 0) {
+    ZT_TRY(scratch(c, kOut, batch_out_bound(padded), &d_out));
+    ss = deflate_batch_scratch_bytes(c, padded);
+    ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
   }
   std::vector<uint64_t> oo(m + 1, 0);
+  ZT_TRY(deflate_members_dev(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv, (uint8_t *)d_out, oo.data(),
+                             d_scr, ss, dh, (uint32_t *)d_sums, nullptr));
+  if (sums) ZT_HIP(hipMemcpyAsync(hsums.data(), d_sums, 8 * m, hipMemcpyDeviceToHost, c->aux));
   uint8_t *body_host = nullptr;
   std::vector<uint8_t> stored_host;
   if (ct == 0) {
@@ -280,28 +269,9 @@ int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, con
     }
     oo[m] = tot;
     stored_host.resize(tot);
-    for (size_t k = 0; k < m; ++k) {
-      uint8_t *o = stored_host.data() + oo[k];
-      const uint8_t *src = in[work[k]];
-      for (uint64_t p = 0; p < len[k]; p += 65535) {
-        const uint32_t l = (uint32_t)std::min<uint64_t>(65535, len[k] - p);
-        o[0] = p + l == len[k] ? 1 : 0;
-        o[1] = l & 0xFF;
-        o[2] = l >> 8;
-        o[3] = ~l & 0xFF;
-        o[4] = (~l >> 8) & 0xFF;
-        memcpy(o + 5, src + p, l);
-        o += 5 + l;
-      }
-    }
+    for (size_t k = 0; k < m; ++k) stored_write(in[work[k]], len[k], stored_host.data() + oo[k]);
     body_host = stored_host.data();
   } else {
-    void *d_out, *d_scr;
-    ZT_TRY(scratch(c, kOut, batch_out_bound(padded), &d_out));
-    const size_t ss = deflate_batch_scratch_bytes(c, padded);
-    ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
-    ZT_TRY(deflate_batch_dev_run(c, (const uint8_t *)d_in, m, off.data(), len.data(), ct, lv, (uint8_t *)d_out,
-                                 oo.data(), d_scr, ss, c->stream, dh));
     // The members are framed on the device (prefix | stream | trailer, at
     // their slab offsets) and come back with one copy -- straight into the
     // slab when it is a registered pool buffer (a caller batching again after
@@ -310,7 +280,7 @@ int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, con
     // quarter of a device thread's host time on a node's worth of devices
     // (tools/c4_host_stages.py).
     const double t_frame = now_ms();
-    const uint32_t plen = (uint32_t)fr.prefix.size(), tl = (uint32_t)fr.trailer;
+    const uint32_t plen = fr.prefix_len(), tl = fr.trailer_len();
     std::vector<FrameItem> fi(m);
     std::vector<size_t> soff(m);
     size_t tot = 0;
@@ -327,14 +297,9 @@ int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, con
     uint8_t *d_prefix = d_framed + fr_bytes + it_bytes;
     ZT_HIP(hipMemcpyAsync(d_items, fi.data(), m * sizeof(FrameItem), hipMemcpyHostToDevice, c->stream));
     if (plen) ZT_HIP(hipMemcpyAsync(d_prefix, fr.prefix.data(), plen, hipMemcpyHostToDevice, c->stream));
-    if (sums) {  // (the trailers need the checksums from the second stream)
-      ZT_HIP(hipEventRecord(c->aux_ev, c->aux));
-      ZT_HIP(hipStreamWaitEvent(c->stream, c->aux_ev, 0));
-    }
-    ZT_TRY(frame_members_dev(d_items, (uint32_t)m, d_prefix, plen,
-                             fr.kind == Framing::GZIP ? 8u : fr.kind == Framing::ZLIB ? 4u : 0u,
-                             static_cast<const uint8_t *>(d_out), static_cast<const uint32_t *>(d_sums), d_framed,
-                             c->stream));
+    if (sums) ZT_TRY(join_sums(c));  // (the trailers need the checksums from the second stream)
+    ZT_TRY(frame_members_dev(d_items, (uint32_t)m, d_prefix, plen, fr.kind, static_cast<const uint8_t *>(d_out),
+                             static_cast<const uint32_t *>(d_sums), d_framed, c->stream));
     uint8_t *slab = slab_out(tot, m, true);
     if (!slab) return set_error(ZT_E_NOMEM, "host allocation failed");
     const bool direct = host_direct(slab, tot);
@@ -375,7 +340,7 @@ int batch_on_device(DeviceCtx *c, const uint8_t *const *in, const size_t *n, con
 
 // split over the batch devices (LPT); a failed share fails the call: every
 // output is released and the first code and message are the caller's
-int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, int lv, const Framing &fr,
+int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, int lv, const MemberFrame &fr,
               uint8_t **out, size_t *out_len, int *status, const HostDict &hd = HostDict()) {
   for (size_t i = 0; i < count; ++i) {
     out[i] = nullptr;
@@ -406,17 +371,11 @@ int run_batch(const uint8_t *const *in, const size_t *n, size_t count, int ct, i
 }  // namespace
 
 // zt_dict.h's batch deflate calls (dict_api.cpp): raw streams, or zlib members
-// whose header carries FDICT and the dictionary's Adler-32
+// whose header carries FDICT and the dictionary's Adler-32 (frame_zlib_dict)
 int deflate_batch_host(const uint8_t *const *in, const size_t *n, size_t count, const zt_deflate_opts *opts,
-                       const HostDict &hd, bool zlib, uint32_t dictid, uint8_t **out, size_t *out_len, int *status) {
+                       const HostDict &hd, const MemberFrame &fr, uint8_t **out, size_t *out_len, int *status) {
   int ct, lv;
   ZT_TRY(resolve_opts(opts, &ct, &lv));
-  Framing fr{Framing::RAW, {}, 0};
-  if (zlib) {
-    uint8_t h6[6];
-    zlib_dict_header(0x78, (uint32_t)(opts ? opts->compression_type : 2), dictid, h6);
-    fr = Framing{Framing::ZLIB, std::vector<uint8_t>(h6, h6 + 6), 4};
-  }
   return run_batch(in, n, count, ct, lv, fr, out, out_len, status, hd);
 }
 
@@ -432,8 +391,7 @@ int zt_deflate_raw_batch(const uint8_t *const *in, const size_t *n, size_t count
   if (!in || !n || !out || !out_len || !status) return set_error(ZT_E_ARG, "null argument");
   int ct, lv;
   ZT_TRY(resolve_opts(opts, &ct, &lv));
-  Framing fr{Framing::RAW, {}, 0};
-  return run_batch(in, n, count, ct, lv, fr, out, out_len, status);
+  return run_batch(in, n, count, ct, lv, frame_raw(), out, out_len, status);
 }
 
 int zt_gzip_compress_batch(const uint8_t *const *in, const size_t *n, size_t count, const zt_gzip_opts *opts,
@@ -442,9 +400,7 @@ int zt_gzip_compress_batch(const uint8_t *const *in, const size_t *n, size_t cou
   if (!in || !n || !out || !out_len || !status) return set_error(ZT_E_ARG, "null argument");
   int ct, lv;
   ZT_TRY(resolve_opts(opts ? &opts->deflate : nullptr, &ct, &lv));
-  Framing fr{Framing::GZIP, {}, 8};
-  gzip_header(opts, fr.prefix);
-  return run_batch(in, n, count, ct, lv, fr, out, out_len, status);
+  return run_batch(in, n, count, ct, lv, frame_gzip(opts), out, out_len, status);
 }
 
 int zt_crc32_batch(const uint8_t *const *in, const size_t *n, size_t count, uint32_t *crc_out) {
@@ -474,9 +430,7 @@ int zt_zlib_compress_batch(const uint8_t *const *in, const size_t *n, size_t cou
   if (!in || !n || !out || !out_len || !status) return set_error(ZT_E_ARG, "null argument");
   int ct, lv;
   ZT_TRY(resolve_opts(opts, &ct, &lv));
-  const uint32_t cmf = 0x78, flg0 = (uint32_t)(opts ? opts->compression_type : 2) << 6;
-  Framing fr{Framing::ZLIB, {(uint8_t)cmf, (uint8_t)(flg0 | (31 - ((cmf << 8) + flg0) % 31))}, 4};
-  return run_batch(in, n, count, ct, lv, fr, out, out_len, status);
+  return run_batch(in, n, count, ct, lv, frame_zlib(opts ? opts->compression_type : 2), out, out_len, status);
 }
 
 }  // extern "C"

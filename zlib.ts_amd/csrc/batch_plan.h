@@ -14,6 +14,7 @@
 
 #include "../../include/zt.h"
 #include "inflate_chain.h"  // align_up
+#include "member_frame.h"   // stored_len
 
 namespace zt {
 
@@ -110,8 +111,6 @@ inline std::vector<size_t> group_cuts(const std::vector<size_t> &off, size_t m, 
 }
 
 // ---- sizes --------------------------------------------------------------------
-// n bytes as stored blocks of <= 65535 bytes (src/RawDeflate.ts:93-100,122-153)
-inline size_t stored_len(size_t n) { return n + 5 * ((n + 65534) / 65535); }
 // Output bound of one deflate call; pipeline_bound = deflate_bound_bytes(n)
 inline size_t deflate_out_bound(int ctype, size_t n, size_t pipeline_bound) {
   if (ctype == 0) return stored_len(n) + 16;

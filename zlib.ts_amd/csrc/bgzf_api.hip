@@ -424,6 +424,7 @@ struct WritePlan {
 // compression type NONE (or level 0): stored blocks, written on the host as the
 // batch calls do; the CRCs alone come from the device
 int write_stored(const WritePlan &W, uint8_t *out, uint64_t *total, std::vector<GziPair> *pairs) {
+  const MemberFrame fr = frame_bgzf();
   uint64_t at = 0;
   for (size_t g = 0; g < W.ng; ++g) {
     const size_t k0 = g * W.G, nb = W.blocks_of(g);
@@ -439,19 +440,11 @@ int write_stored(const WritePlan &W, uint8_t *out, uint64_t *total, std::vector<
       const uint32_t l = (uint32_t)len[j], size = kBgzfHeaderBytes + 5 + l + kBgzfTrailerBytes;
       if (k0 + j) pairs->push_back(GziPair{at, (uint64_t)(k0 + j) * W.bs});
       uint8_t *o = out + at;
-      memcpy(o, bgzf_eof_marker(), kBgzfHeaderBytes);
+      memcpy(o, fr.prefix.data(), kBgzfHeaderBytes);
       o[16] = (uint8_t)((size - 1) & 0xFF);
       o[17] = (uint8_t)((size - 1) >> 8);
-      o += kBgzfHeaderBytes;
-      o[0] = 1;
-      o[1] = l & 0xFF;
-      o[2] = l >> 8;
-      o[3] = ~l & 0xFF;
-      o[4] = (~l >> 8) & 0xFF;
-      memcpy(o + 5, ptr[j], l);
-      o += 5 + l;
-      for (int k = 0; k < 4; ++k) o[k] = (crc[j] >> (8 * k)) & 0xFF;
-      for (int k = 0; k < 4; ++k) o[4 + k] = (l >> (8 * k)) & 0xFF;
+      stored_write(ptr[j], l, o + kBgzfHeaderBytes);
+      put_trailer(o + kBgzfHeaderBytes + 5 + l, fr.kind, crc[j], 1, l);
       at += size;
     }
   }
@@ -492,7 +485,8 @@ int write_pipeline(DeviceCtx *c, const WritePlan &W, uint8_t *out, uint64_t *tot
   stage_in[1] = static_cast<uint8_t *>(p);
   ZT_TRY(pinned(c, fr_cap, &p, kPinGroupOut));
   stage_out = static_cast<uint8_t *>(p);
-  ZT_HIP(hipMemcpyAsync(d_prefix, bgzf_eof_marker(), kBgzfHeaderBytes, hipMemcpyHostToDevice, c->stream));
+  const MemberFrame fr = frame_bgzf();
+  ZT_HIP(hipMemcpyAsync(d_prefix, fr.prefix.data(), kBgzfHeaderBytes, hipMemcpyHostToDevice, c->stream));
   ZT_HIP(hipStreamSynchronize(c->stream));
 
   std::vector<uint64_t> goff(ng + 1, 0);  // group g's bytes in the file
@@ -521,12 +515,8 @@ int write_pipeline(DeviceCtx *c, const WritePlan &W, uint8_t *out, uint64_t *tot
       ro[j] = j * W.cell;
       rl[j] = W.slice_len(k0 + j);
     }
-    // checksums on the second stream, over the same device bytes
-    ZT_HIP(hipStreamWaitEvent(c->aux, pipe.landed(g), 0));
-    ZT_TRY(checksums_batch_dev(c, d_in[g & 1], nb, ro.data(), rl.data(), static_cast<uint32_t *>(d_sums), c->aux));
-    ZT_HIP(hipEventRecord(c->aux_ev, c->aux));
-    ZT_TRY(deflate_batch_dev_run(c, d_in[g & 1], nb, ro.data(), rl.data(), W.ct, W.lv, static_cast<uint8_t *>(d_body),
-                                 oo.data(), d_scr, ss, c->stream));
+    ZT_TRY(deflate_members_dev(c, d_in[g & 1], nb, ro.data(), rl.data(), W.ct, W.lv, static_cast<uint8_t *>(d_body),
+                               oo.data(), d_scr, ss, nullptr, static_cast<uint32_t *>(d_sums), pipe.landed(g)));
     // the blocks' sizes and dense places
     uint64_t at = 0;
     for (size_t j = 0; j < nb; ++j) {
@@ -548,8 +538,8 @@ int write_pipeline(DeviceCtx *c, const WritePlan &W, uint8_t *out, uint64_t *tot
     }
     goff[g + 1] = goff[g] + at;
     ZT_HIP(hipMemcpyAsync(d_items[g & 1], fi.data(), items * sizeof(FrameItem), hipMemcpyHostToDevice, c->stream));
-    ZT_HIP(hipStreamWaitEvent(c->stream, c->aux_ev, 0));  // (the trailers need the checksums)
-    ZT_TRY(frame_members_dev(d_items[g & 1], (uint32_t)items, d_prefix, kBgzfHeaderBytes, kBgzfTrailerBytes,
+    ZT_TRY(join_sums(c));  // (the trailers need the checksums)
+    ZT_TRY(frame_members_dev(d_items[g & 1], (uint32_t)items, d_prefix, kBgzfHeaderBytes, fr.kind,
                              static_cast<const uint8_t *>(d_body), static_cast<const uint32_t *>(d_sums),
                              d_framed[g & 1], c->stream, 16));
     // (the download stage copies on its own stream; fi, d_body and d_sums are the next group's)

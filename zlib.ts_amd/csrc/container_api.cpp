@@ -90,41 +90,24 @@ int deflate_with_checksums(const uint8_t *in, size_t n, const zt_deflate_opts *o
   return ZT_OK;
 }
 
-void put32le(uint8_t *p, uint32_t v) {
-  p[0] = v & 0xFF;
-  p[1] = (v >> 8) & 0xFF;
-  p[2] = (v >> 16) & 0xFF;
-  p[3] = v >> 24;
+// One member from one host buffer: zt_gzip_compress and zt_zlib_compress, and
+// with idx non-null their _indexed forms.  *sum_out: the trailer's checksum.
+int compress_member_host(const MemberFrame &fr, const uint8_t *in, size_t n, const zt_deflate_opts *opts,
+                         uint8_t **out, size_t *out_len, uint32_t *sum_out, uint8_t **idx, size_t *idx_len) {
+  uint8_t *buf;
+  size_t slen;
+  uint32_t crc = 0, adler = 1;
+  const bool gz = fr.kind == kFmtGzip;
+  ZT_TRY(deflate_with_checksums(in, n, opts, fr.prefix.data(), fr.prefix.size(), fr.trailer_len(), &buf, &slen,
+                                gz ? &crc : nullptr, gz ? nullptr : &adler, idx, idx_len));
+  put_trailer(buf + fr.prefix.size() + slen, fr.kind, crc, adler, (uint32_t)n);
+  *out = buf;
+  *out_len = fr.prefix.size() + slen + fr.trailer_len();
+  if (sum_out) *sum_out = gz ? crc : adler;
+  return ZT_OK;
 }
 
 }  // namespace
-
-// member header: src/GZip.ts:104-158
-void gzip_header(const zt_gzip_opts *opts, std::vector<uint8_t> &hd) {
-  hd = {0x1F, 0x8B, 8};
-  uint8_t flg = 0;
-  if (opts && opts->fname) flg |= 0x08;
-  if (opts && opts->fcomment) flg |= 0x10;
-  if (opts && opts->fhcrc) flg |= 0x02;
-  hd.push_back(flg);
-  const uint32_t mtime = opts ? opts->mtime : 0;
-  for (int k = 0; k < 4; ++k) hd.push_back((mtime >> (8 * k)) & 0xFF);
-  hd.push_back(0);  // XFL
-  hd.push_back(3);  // OS: UNIX (src/GZip.ts:128)
-  if (opts && opts->fname) {
-    hd.insert(hd.end(), opts->name, opts->name + opts->name_len);
-    hd.push_back(0);
-  }
-  if (opts && opts->fcomment) {
-    hd.insert(hd.end(), opts->comment, opts->comment + opts->comment_len);
-    hd.push_back(0);
-  }
-  if (opts && opts->fhcrc) {
-    const uint32_t c16 = crc32_small(hd.data(), hd.size()) & 0xFFFF;
-    hd.push_back(c16 & 0xFF);
-    hd.push_back(c16 >> 8);
-  }
-}
 }  // namespace zt
 
 using namespace zt;
@@ -136,20 +119,8 @@ static int gzip_compress_host(const uint8_t *in, size_t n, const zt_gzip_opts *o
                               uint32_t *crc_out, uint8_t **idx, size_t *idx_len) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
-  std::vector<uint8_t> hd;
-  gzip_header(opts, hd);
-  uint8_t *buf;
-  size_t slen;
-  uint32_t crc;
-  ZT_TRY(deflate_with_checksums(in, n, opts ? &opts->deflate : nullptr, hd.data(), hd.size(), 8, &buf, &slen, &crc,
-                                nullptr, idx, idx_len));
-  // trailer: CRC-32 and ISIZE (src/GZip.ts:179-185)
-  put32le(buf + hd.size() + slen, crc);
-  put32le(buf + hd.size() + slen + 4, (uint32_t)n);
-  *out = buf;
-  *out_len = hd.size() + slen + 8;
-  if (crc_out) *crc_out = crc;
-  return ZT_OK;
+  return compress_member_host(frame_gzip(opts), in, n, opts ? &opts->deflate : nullptr, out, out_len, crc_out, idx,
+                              idx_len);
 }
 
 int zt_gzip_compress(const uint8_t *in, size_t n, const zt_gzip_opts *opts, uint8_t **out, size_t *out_len,
@@ -235,23 +206,7 @@ static int zlib_compress_host(const uint8_t *in, size_t n, const zt_deflate_opts
   if (n && !in) return set_error(ZT_E_ARG, "null input");
   const int ct = opts ? opts->compression_type : 2;
   if (ct < 0 || ct > 2) return set_error(ZT_E_INVALID_COMPRESSION_TYPE, "invalid compression type");
-  // CMF = 0x78 (deflate, 32 KiB window); FLG: FLEVEL = compressionType, FCHECK (src/Deflate.ts:61-78)
-  const uint32_t cmf = 0x78, flg0 = (uint32_t)ct << 6;
-  const uint8_t hd[2] = {(uint8_t)cmf, (uint8_t)(flg0 | (31 - ((cmf << 8) + flg0) % 31))};
-  uint8_t *buf;
-  size_t slen;
-  uint32_t adler;
-  ZT_TRY(deflate_with_checksums(in, n, opts, hd, 2, 4, &buf, &slen, nullptr, &adler, idx, idx_len));
-  // Adler-32, big-endian (src/Deflate.ts:95)
-  uint8_t *t = buf + 2 + slen;
-  t[0] = adler >> 24;
-  t[1] = (adler >> 16) & 0xFF;
-  t[2] = (adler >> 8) & 0xFF;
-  t[3] = adler & 0xFF;
-  *out = buf;
-  *out_len = 2 + slen + 4;
-  if (adler_out) *adler_out = adler;
-  return ZT_OK;
+  return compress_member_host(frame_zlib(ct), in, n, opts, out, out_len, adler_out, idx, idx_len);
 }
 
 int zt_zlib_compress(const uint8_t *in, size_t n, const zt_deflate_opts *opts, uint8_t **out, size_t *out_len,
@@ -272,20 +227,15 @@ int zt_zlib_decompress(const uint8_t *in, size_t n, size_t index, int verify, ui
                        size_t *end_ip, uint32_t *adler_out) {
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if (n && !in) return set_error(ZT_E_ARG, "null input");
-  Reader b{in, n, index};
-  const int cmf = b.byte(), flg = b.byte();
-  char msg[96];
   // src/Inflate.ts:44-58
-  if (cmf < 0 || (cmf & 0x0F) != 8) return set_error(ZT_E_ZLIB_METHOD, "unsupported compression method");
-  if (flg < 0) return set_error(ZT_E_ZLIB_FCHECK, "invalid fcheck flag:NaN");
-  if (((cmf << 8) + flg) % 31 != 0) {
-    snprintf(msg, sizeof msg, "invalid fcheck flag:%d", ((cmf << 8) + flg) % 31);
-    return set_error(ZT_E_ZLIB_FCHECK, msg);
-  }
-  if (flg & 0x20) return set_error(ZT_E_ZLIB_FDICT, "fdict flag is not supported");
+  ZlibHeader h;
+  int code;
+  std::string msg;
+  if (zlib_header_status(zlib_parse_header(in, n, index, &h), h, &code, &msg)) return set_error(code, msg);
+  if (h.fdict) return set_error(ZT_E_ZLIB_FDICT, "fdict flag is not supported");
   uint8_t *o = nullptr;
   size_t olen = 0, eip = 0;
-  ZT_TRY(zt_inflate_raw(in, n, b.p, nullptr, &o, &olen, &eip));
+  ZT_TRY(zt_inflate_raw(in, n, index + 2, nullptr, &o, &olen, &eip));
   uint32_t adler = 1;
   if (verify) {
     // src/Inflate.ts:80-90 (the Adler-32 of the output, on the GPU)

@@ -347,12 +347,10 @@ int zlib_share_locked(DeviceCtx *c, const ZlibArgs &A, const std::vector<size_t>
     };
     ZlibHeader h;
     const ZlibHdr hs = zlib_parse_header(A.in[i], A.n[i], A.index ? A.index[i] : 0, &h);
-    if (hs == ZH_METHOD) {
-      fail(ZT_E_ZLIB_METHOD, "unsupported compression method");
-    } else if (hs == ZH_FCHECK_NAN) {
-      fail(ZT_E_ZLIB_FCHECK, "invalid fcheck flag:NaN");
-    } else if (hs == ZH_FCHECK) {
-      fail(ZT_E_ZLIB_FCHECK, "invalid fcheck flag:" + std::to_string(h.fcheck));
+    int code;
+    std::string hmsg;
+    if (zlib_header_status(hs, h, &code, &hmsg)) {
+      fail(code, hmsg);
     } else if (h.fdict && A.dict_len == 0) {
       fail(ZT_E_ZLIB_FDICT, "fdict flag is not supported");
     } else if (hs == ZH_BROKEN) {

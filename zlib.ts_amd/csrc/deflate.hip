@@ -1914,6 +1914,24 @@ int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const
   return ZT_OK;
 }
 
+// (zt_internal.h: the member writers' compute step)
+int deflate_members_dev(DeviceCtx *c, const uint8_t *d_in, size_t count, const uint64_t *off, const uint64_t *len,
+                        int ctype, int level, uint8_t *d_body, uint64_t *out_off, void *scratch_base,
+                        size_t scratch_size, const DictHist *dict, uint32_t *d_sums, hipEvent_t landed) {
+  if (d_sums) {  // on the second stream, over the same device bytes
+    if (!landed) {
+      ZT_HIP(hipEventRecord(c->aux_ev, c->stream));
+      landed = c->aux_ev;
+    }
+    ZT_HIP(hipStreamWaitEvent(c->aux, landed, 0));
+    ZT_TRY(checksums_batch_dev(c, d_in, count, off, len, d_sums, c->aux));
+    ZT_HIP(hipEventRecord(c->aux_ev, c->aux));
+  }
+  if (ctype == 0) return ZT_OK;  // (stored blocks are the caller's framing)
+  return deflate_batch_dev_run(c, d_in, count, off, len, ctype, level, d_body, out_off, scratch_base, scratch_size,
+                               c->stream, dict);
+}
+
 // blocks that measured through the queues, blocks that measured at once,
 // since the last call (of the current device)
 extern "C" int zt_debug_head_formats(uint64_t out[2]) {

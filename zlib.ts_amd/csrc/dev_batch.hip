@@ -1,9 +1,9 @@
 // dev_batch.hip -- the two ends of the device-resident batch calls
 // (include/zt_dev_batch.h; the job tables: dev_batch_plan.h): dev_copy_kernel
 // gathers the caller's buffers into the layout the batch pipelines read and
-// scatters their results to the caller's pointers; dev_patch_kernel writes the
-// few bytes around them (prefixes, trailers with the checksums, stored-block
-// headers).
+// scatters their results to the caller's pointers.  The few bytes around them
+// (prefixes, trailers with the checksums, stored-block headers) are
+// dev_patch_kernel's, in member_frame.hip.
 #include "zt_internal.h"
 
 namespace zt {
@@ -71,38 +71,12 @@ __global__ __launch_bounds__(256) void dev_copy_kernel(const DevCopyJob *__restr
   for (uint32_t i = body + threadIdx.x; i < n; i += 256) d[i] = s[i];
 }
 
-// one thread per patch job (DevPatchJob: dev_batch_plan.h)
-__global__ __launch_bounds__(256) void dev_patch_kernel(const DevPatchJob *__restrict__ jobs, uint32_t njobs,
-                                                        const uint32_t *__restrict__ sums) {
-  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= njobs) return;
-  const DevPatchJob j = jobs[t];
-  uint8_t *d = reinterpret_cast<uint8_t *>(j.dst);
-  if (j.kind == kPatchGzipTrailer) {  // CRC-32, ISIZE (src/GZip.ts:179-185)
-    const uint32_t crc = sums[2 * (size_t)j.sum], isize = (uint32_t)j.value;
-    for (int k = 0; k < 4; ++k) d[k] = (uint8_t)(crc >> (8 * k));
-    for (int k = 0; k < 4; ++k) d[4 + k] = (uint8_t)(isize >> (8 * k));
-  } else if (j.kind == kPatchZlibTrailer) {  // Adler-32 big endian (src/Deflate.ts:95)
-    const uint32_t ad = sums[2 * (size_t)j.sum + 1];
-    for (int k = 0; k < 4; ++k) d[k] = (uint8_t)(ad >> (24 - 8 * k));
-  } else {
-    for (uint32_t k = 0; k < j.len && k < 8; ++k) d[k] = (uint8_t)(j.value >> (8 * k));
-  }
-}
-
 }  // namespace
 
 int dev_copy_dev(const DevCopyJob *d_jobs, uint32_t njobs, uint64_t tiles, hipStream_t s) {
   if (tiles == 0 || njobs == 0) return ZT_OK;
   if (tiles > kDevMaxTiles) return set_error(ZT_E_ARG, "batch too large for one launch");
   dev_copy_kernel<<<(uint32_t)tiles, 256, 0, s>>>(d_jobs, njobs);
-  ZT_HIP(hipGetLastError());
-  return ZT_OK;
-}
-
-int dev_patch_dev(const DevPatchJob *d_jobs, uint32_t njobs, const uint32_t *d_sums, hipStream_t s) {
-  if (njobs == 0) return ZT_OK;
-  dev_patch_kernel<<<(njobs + 255) / 256, 256, 0, s>>>(d_jobs, njobs, d_sums);
   ZT_HIP(hipGetLastError());
   return ZT_OK;
 }

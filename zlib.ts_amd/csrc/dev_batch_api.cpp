@@ -11,8 +11,8 @@
 // (deflate_batch_dev_run with checksums_batch_dev beside it on the second
 // stream; the batch decoder of inflate_api.cpp, both routes, through its
 // device sink); dev_copy_kernel scatters the results to the caller's pointers
-// and dev_patch_kernel writes prefixes, trailers and stored-block headers
-// around them.  Items whose result does not fit are masked out on the host,
+// and dev_patch_kernel (member_frame.hip) writes prefixes, trailers and
+// stored-block headers around them.  Items whose result does not fit are masked out on the host,
 // where every length is known before the scatter is planned
 // (dev_batch_plan.h: the arithmetic, checked by tools/dev_batch_host_check.cpp).
 #include <algorithm>
@@ -124,14 +124,14 @@ uint64_t group_bytes(uint64_t dflt = kDevGroupBytes) {
 int too_many_tiles() { return set_error(ZT_E_ARG, "batch too large for one launch"); }
 
 // ---- deflate ------------------------------------------------------------------
-// ct: the resolved compression type (0 for level 0); ct_opt: as the caller
-// gave it (zlib's FLEVEL, as zt_zlib_compress_batch writes it)
-int deflate_groups(DeviceCtx *c, const uint64_t *src, const size_t *n, size_t count, int ct, int ct_opt, int lv,
-                   int fmt, const uint64_t *dst, const size_t *out_cap, size_t *out_len, int *status) {
+// ct: the resolved compression type (0 for level 0)
+int deflate_groups(DeviceCtx *c, const uint64_t *src, const size_t *n, size_t count, int ct, int lv,
+                   const MemberFrame &fr, const uint64_t *dst, const size_t *out_cap, size_t *out_len, int *status) {
   hipStream_t s = c->stream;
-  const bool sums = fmt != kFmtRaw;
-  uint8_t prefix[10];
-  const uint32_t plen = dev_prefix(fmt, ct_opt, prefix), tl = dev_trailer_len(fmt);
+  const bool sums = fr.kind != kFmtRaw;
+  const uint32_t plen = fr.prefix_len(), tl = fr.trailer_len();
+  uint8_t empty_trailer[8];  // CRC-32 0, ISIZE 0; Adler-32 1
+  put_trailer(empty_trailer, fr.kind, 0, 1, 0);
   const std::vector<size_t> all = iota_ids(count);
   const std::vector<size_t> cut = dev_group_cuts(n, all, kDevBlk, group_bytes());
   std::list<Launch> keep;
@@ -153,21 +153,17 @@ int deflate_groups(DeviceCtx *c, const uint64_t *src, const size_t *n, size_t co
       Launch ga;
       if (dev_gather_plan(src, n, pk, L, reinterpret_cast<uint64_t>(d_in), true, ga.cp)) return too_many_tiles();
       ZT_TRY(run_launch(c, keep, std::move(ga), nullptr, s, kGather));
-      if (sums) {  // on the second stream, over the same device bytes
-        ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
-        ZT_HIP(hipEventRecord(c->aux_ev, s));
-        ZT_HIP(hipStreamWaitEvent(c->aux, c->aux_ev, 0));
-        ZT_TRY(checksums_batch_dev(c, static_cast<const uint8_t *>(d_in), m, L.off.data(), len.data(),
-                                   static_cast<uint32_t *>(d_sums), c->aux));
-      }
+      void *d_scr = nullptr;
+      size_t ss = 0;
+      if (sums) ZT_TRY(scratch(c, kSums, 8 * m, &d_sums));
       if (ct != 0) {
-        void *d_scr;
         ZT_TRY(scratch(c, kOut, batch_out_bound(L.total), &d_body));
-        const size_t ss = deflate_batch_scratch_bytes(c, L.total);
+        ss = deflate_batch_scratch_bytes(c, L.total);
         ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
-        ZT_TRY(deflate_batch_dev_run(c, static_cast<const uint8_t *>(d_in), m, L.off.data(), len.data(), ct, lv,
-                                     static_cast<uint8_t *>(d_body), oo.data(), d_scr, ss, s));
       }
+      ZT_TRY(deflate_members_dev(c, static_cast<const uint8_t *>(d_in), m, L.off.data(), len.data(), ct, lv,
+                                 static_cast<uint8_t *>(d_body), oo.data(), d_scr, ss, nullptr,
+                                 static_cast<uint32_t *>(d_sums), nullptr));
     }
     // the scatter: prefix | body | trailer of every item that fits
     Launch sc;
@@ -176,7 +172,7 @@ int deflate_groups(DeviceCtx *c, const uint64_t *src, const size_t *n, size_t co
       const bool packed = n[i] && (ct != 0 || sums);
       const size_t kk = packed ? k++ : 0;
       const bool piped = n[i] && ct != 0;
-      const uint64_t body = piped ? oo[kk + 1] - oo[kk] : dev_stored_len(n[i]);
+      const uint64_t body = piped ? oo[kk + 1] - oo[kk] : stored_len(n[i]);
       const uint64_t need = plen + body + tl;
       out_len[i] = need;
       status[i] = ZT_OK;
@@ -185,24 +181,18 @@ int deflate_groups(DeviceCtx *c, const uint64_t *src, const size_t *n, size_t co
         continue;
       }
       if (!dst[i]) return set_error(ZT_E_ARG, "null output");
-      dev_patch_prefix(sc.pj, dst[i], prefix, plen);
+      dev_patch_bytes(sc.pj, dst[i], fr.prefix.data(), plen);
       if (piped) {
         if (!sc.cp.add(reinterpret_cast<uint64_t>(d_body) + oo[kk], dst[i] + plen, body)) return too_many_tiles();
       } else if (!dev_stored_jobs(src[i], n[i], dst[i] + plen, sc.cp, sc.pj)) {
         return too_many_tiles();
       }
-      if (n[i]) {
-        dev_patch_trailer(sc.pj, fmt, dst[i] + plen + body, n[i], (uint32_t)kk);
-      } else if (fmt == kFmtGzip) {  // CRC-32 0, ISIZE 0
-        sc.pj.push_back(DevPatchJob{dst[i] + plen + body, 0, 8, kPatchBytes, 0, 0});
-      } else if (fmt == kFmtZlib) {  // Adler-32 1, big endian
-        sc.pj.push_back(DevPatchJob{dst[i] + plen + body, 0x01000000ull, 4, kPatchBytes, 0, 0});
-      }
+      if (n[i])
+        dev_patch_trailer(sc.pj, fr.kind, dst[i] + plen + body, n[i], (uint32_t)kk);
+      else  // (no sums: the empty input goes through no gather)
+        dev_patch_bytes(sc.pj, dst[i] + plen + body, empty_trailer, tl);
     }
-    if (m && sums) {  // (the trailers need the checksums from the second stream)
-      ZT_HIP(hipEventRecord(c->aux_ev, c->aux));
-      ZT_HIP(hipStreamWaitEvent(s, c->aux_ev, 0));
-    }
+    if (m && sums) ZT_TRY(join_sums(c));  // (the trailers need the checksums from the second stream)
     ZT_TRY(run_launch(c, keep, std::move(sc), static_cast<const uint32_t *>(d_sums), s, kScatter));
     // the next group reuses kIn, kOut and kSums; the last group's work stays
     // queued for the caller's stream
@@ -321,7 +311,7 @@ int zt_debug_dev_batch_times(int enable, double out[2]) {
 
 size_t zt_deflate_dev_batch_bound(size_t n, int compression_type, int format) {
   if (compression_type < 0 || compression_type > 2 || format < kFmtRaw || format > kFmtGzip) return 0;
-  return (size_t)dev_batch_bound(n, compression_type, format);
+  return (size_t)dev_batch_bound(n, compression_type, (MemberKind)format);
 }
 
 int zt_deflate_dev_batch(const void *const *d_in, const size_t *n, size_t count, const zt_deflate_opts *opts,
@@ -344,8 +334,10 @@ int zt_deflate_dev_batch(const void *const *d_in, const size_t *n, size_t count,
   }
   StreamBridge br(c, stream);
   ZT_TRY(br.enter());
-  const int rc = deflate_groups(c, src.data(), n, count, ct, opts ? opts->compression_type : 2, lv, format,
-                                dst.data(), out_cap, out_len, status);
+  // (zlib's FLEVEL: the compression type as given, as zt_zlib_compress_batch writes it)
+  const int rc = deflate_groups(c, src.data(), n, count, ct, lv,
+                                frame_of((MemberKind)format, opts ? opts->compression_type : 2), dst.data(), out_cap,
+                                out_len, status);
   const std::string msg = rc ? zt_last_error_message() : "";
   if (const int lrc = br.leave()) return rc ? set_error(rc, msg) : lrc;
   return rc ? set_error(rc, msg) : ZT_OK;

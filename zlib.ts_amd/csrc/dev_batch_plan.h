@@ -1,7 +1,8 @@
 // dev_batch_plan.h -- the arithmetic of the device-resident batch calls
 // (include/zt_dev_batch.h), no HIP: the copy jobs and their tile table for the
 // gather and scatter kernels (dev_batch.hip), the patch jobs (prefixes,
-// trailers, stored-block headers), the stored-block job list of compression
+// trailers, stored-block headers: member_frame.h's bytes, written by
+// member_frame.hip's dev_patch_kernel), the stored-block job list of compression
 // type NONE, the output bound, the groups a large batch is cut into and the
 // capacity masking.  Pointers are carried as integers and never dereferenced
 // here.  Pure functions, checked on the CPU under ASan / UBSan by
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "batch_plan.h"
+#include "member_frame.h"
 
 namespace zt {
 
@@ -43,15 +45,15 @@ struct DevCopyJob {
   uint64_t src, dst, len;
   uint32_t tile0, zero;
 };
-// A few bytes written by one thread.  kind 0: the `len` <= 8 low bytes of
-// `value`, little endian.  kind 1 (gzip trailer): CRC-32 of sums[2 sum], then
-// the low 32 bits of value (ISIZE), both little endian.  kind 2 (zlib
-// trailer): Adler-32 sums[2 sum + 1], big endian.
+// A few bytes written by one thread.  kind kPatchBytes: the `len` <= 8 low
+// bytes of `value`, little endian.  kind kFmtGzip or kFmtZlib: that member
+// kind's trailer (put_trailer) with CRC-32 sums[2 sum], Adler-32
+// sums[2 sum + 1] and the low 32 bits of value as ISIZE.
 struct DevPatchJob {
   uint64_t dst, value;
   uint32_t len, kind, sum, pad;
 };
-enum : uint32_t { kPatchBytes = 0, kPatchGzipTrailer = 1, kPatchZlibTrailer = 2 };
+constexpr uint32_t kPatchBytes = kFmtRaw;  // (a raw member has no trailer job)
 
 struct DevCopyPlan {
   std::vector<DevCopyJob> jobs;
@@ -81,65 +83,37 @@ inline size_t dev_copy_find(const std::vector<DevCopyJob> &jobs, uint32_t tile) 
   return lo;
 }
 
-// ---- framing ------------------------------------------------------------------
-enum : int { kFmtRaw = 0, kFmtZlib = 1, kFmtGzip = 2 };
-inline uint32_t dev_prefix_len(int fmt) { return fmt == kFmtGzip ? 10u : fmt == kFmtZlib ? 2u : 0u; }
-inline uint32_t dev_trailer_len(int fmt) { return fmt == kFmtGzip ? 8u : fmt == kFmtZlib ? 4u : 0u; }
-// the prefix bytes: gzip's fixed 10-byte header (no name, no comment, mtime 0,
-// OS 3), zlib's CMF 0x78 | FLG with FLEVEL = the caller's compression type
-// (`ctype_opt`: as given, before level 0 turns it into 0) -- what
-// zt_gzip_compress_batch and zt_zlib_compress_batch write
-inline uint32_t dev_prefix(int fmt, int ctype_opt, uint8_t p[10]) {
-  if (fmt == kFmtGzip) {
-    const uint8_t h[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 3};
-    for (int k = 0; k < 10; ++k) p[k] = h[k];
-    return 10;
-  }
-  if (fmt == kFmtZlib) {
-    const uint32_t cmf = 0x78, flg0 = (uint32_t)ctype_opt << 6;
-    p[0] = (uint8_t)cmf;
-    p[1] = (uint8_t)(flg0 | (31 - ((cmf << 8) + flg0) % 31));
-    return 2;
-  }
-  return 0;
-}
-// prefix of `plen` <= 10 bytes at dst: one or two byte patches
-inline void dev_patch_prefix(std::vector<DevPatchJob> &pj, uint64_t dst, const uint8_t *p, uint32_t plen) {
-  for (uint32_t a = 0; a < plen; a += 8) {
-    const uint32_t l = plen - a < 8 ? plen - a : 8;
+// ---- the jobs of a frame (member_frame.h) --------------------------------------
+// `len` bytes at dst: a byte patch per 8
+inline void dev_patch_bytes(std::vector<DevPatchJob> &pj, uint64_t dst, const uint8_t *p, uint32_t len) {
+  for (uint32_t a = 0; a < len; a += 8) {
+    const uint32_t l = len - a < 8 ? len - a : 8;
     uint64_t v = 0;
     for (uint32_t k = 0; k < l; ++k) v |= (uint64_t)p[a + k] << (8 * k);
     pj.push_back(DevPatchJob{dst + a, v, l, kPatchBytes, 0, 0});
   }
 }
-inline void dev_patch_trailer(std::vector<DevPatchJob> &pj, int fmt, uint64_t dst, uint64_t isize, uint32_t sum) {
-  if (fmt == kFmtGzip) pj.push_back(DevPatchJob{dst, isize & 0xFFFFFFFFull, 8, kPatchGzipTrailer, sum, 0});
-  if (fmt == kFmtZlib) pj.push_back(DevPatchJob{dst, 0, 4, kPatchZlibTrailer, sum, 0});
+// the trailer of a member of isize > 0 input bytes, its checksums at sums[2 sum ..]
+inline void dev_patch_trailer(std::vector<DevPatchJob> &pj, MemberKind kind, uint64_t dst, uint64_t isize,
+                              uint32_t sum) {
+  if (kind != kFmtRaw)
+    pj.push_back(DevPatchJob{dst, isize & 0xFFFFFFFFull, member_trailer_len(kind), (uint32_t)kind, sum, 0});
 }
 
-// ---- stored blocks (compression type NONE, level 0; the empty input) --------------
-// the 5 header bytes of a stored block of l <= 65535 bytes, little endian in a word
-inline uint64_t stored_header(uint32_t l, bool last) {
-  return (uint64_t)(last ? 1 : 0) | (uint64_t)(l & 0xFFFF) << 8 | (uint64_t)(~l & 0xFFFF) << 24;
-}
-// n bytes at src as stored blocks of <= 65535 bytes at dst (stored_len(n)
-// bytes; n == 0: the final empty block): a header patch and a copy job per
-// block.  false: past the tile limit.
+// n bytes at src as stored blocks of <= 65535 bytes at dst (what stored_write
+// writes, stored_len(n) bytes): a header patch and, unless it is empty, a copy
+// job per block.  false: past the tile limit.
 inline bool dev_stored_jobs(uint64_t src, uint64_t n, uint64_t dst, DevCopyPlan &cp, std::vector<DevPatchJob> &pj) {
-  if (n == 0) {
-    pj.push_back(DevPatchJob{dst, stored_header(0, true), 5, kPatchBytes, 0, 0});
-    return true;
-  }
-  for (uint64_t p = 0; p < n; p += 65535) {
+  uint64_t p = 0;
+  do {
     const uint32_t l = (uint32_t)(n - p < 65535 ? n - p : 65535);
     pj.push_back(DevPatchJob{dst, stored_header(l, p + l == n), 5, kPatchBytes, 0, 0});
     if (!cp.add(src + p, dst + 5, l)) return false;
     dst += 5 + (uint64_t)l;
-  }
+    p += l;
+  } while (p < n);
   return true;
 }
-// a body of n input bytes as stored blocks; the empty input's one block
-inline uint64_t dev_stored_len(uint64_t n) { return n ? stored_len(n) : 5; }
 
 // ---- the bound ----------------------------------------------------------------
 // Upper bound of one item's output (zt_deflate_dev_batch_bound), proven from
@@ -156,10 +130,10 @@ inline uint64_t dev_stored_len(uint64_t n) { return n ? stored_len(n) : 5; }
 // bits, the padding and the 4 sync bytes: at most blen + blen / 8 + 7 bytes a
 // block -- inside (blen + 10) + the n / 8 + 64 allowance deflate_out_bound
 // carries for fixed codes.  Type 0: stored_len(n).  n == 0: 5 bytes.
-inline uint64_t dev_batch_bound(uint64_t n, int ctype, int fmt) {
-  const uint64_t frame = dev_prefix_len(fmt) + dev_trailer_len(fmt);
-  if (n == 0) return 5 + frame;
-  if (ctype == 0) return stored_len(n) + frame;
+inline uint64_t dev_batch_bound(uint64_t n, int ctype, MemberKind fmt) {
+  const MemberFrame fr = frame_of(fmt, 0);
+  const uint64_t frame = fr.prefix_len() + fr.trailer_len();
+  if (n == 0 || ctype == 0) return stored_len(n) + frame;
   const uint64_t nb = (n + kDevBlk - 1) / kDevBlk;
   return n + 10 * nb + 10 * ((nb - 1) / 32) + (ctype == 1 ? n / 8 + 64 : 0) + frame;
 }

@@ -66,7 +66,7 @@ int zt_deflate_raw_batch_dict(const uint8_t *const *in, const size_t *n, size_t 
   if (dict_len == 0) return zt_deflate_raw_batch(in, n, count, opts, out, out_len, status);
   if (count == 0) return ZT_OK;
   if (!in || !n || !out || !out_len || !status || !dict) return set_error(ZT_E_ARG, "null argument");
-  return deflate_batch_host(in, n, count, opts, HostDict{dict, dict_len}, false, 0, out, out_len, status);
+  return deflate_batch_host(in, n, count, opts, HostDict{dict, dict_len}, frame_raw(), out, out_len, status);
 }
 
 int zt_deflate_raw_dict(const uint8_t *in, size_t n, const zt_deflate_opts *opts, const uint8_t *dict,
@@ -75,7 +75,7 @@ int zt_deflate_raw_dict(const uint8_t *in, size_t n, const zt_deflate_opts *opts
   if (!out || !out_len) return set_error(ZT_E_ARG, "null output");
   if ((n && !in) || !dict) return set_error(ZT_E_ARG, "null input");
   int st = 0;
-  return deflate_batch_host(&in, &n, 1, opts, HostDict{dict, dict_len}, false, 0, out, out_len, &st);
+  return deflate_batch_host(&in, &n, 1, opts, HostDict{dict, dict_len}, frame_raw(), out, out_len, &st);
 }
 
 int zt_zlib_compress_batch_dict(const uint8_t *const *in, const size_t *n, size_t count,
@@ -86,7 +86,8 @@ int zt_zlib_compress_batch_dict(const uint8_t *const *in, const size_t *n, size_
   if (!in || !n || !out || !out_len || !status || !dict) return set_error(ZT_E_ARG, "null argument");
   uint32_t dictid = 1;
   ZT_TRY(zt_adler32_update(1, dict, dict_len, &dictid));  // (the checksum kernel, over the whole dictionary)
-  return deflate_batch_host(in, n, count, opts, HostDict{dict, dict_len}, true, dictid, out, out_len, status);
+  return deflate_batch_host(in, n, count, opts, HostDict{dict, dict_len},
+                            frame_zlib_dict(opts ? opts->compression_type : 2, dictid), out, out_len, status);
 }
 
 int zt_zlib_compress_dict(const uint8_t *in, size_t n, const zt_deflate_opts *opts, const uint8_t *dict,
@@ -134,7 +135,9 @@ int zt_zlib_decompress_dict(const uint8_t *in, size_t n, size_t index, int verif
   if ((n && !in) || (dict_len && !dict)) return set_error(ZT_E_ARG, "null input");
   ZlibHeader h;
   const ZlibHdr hs = zlib_parse_header(in, n, index, &h);
-  // no FDICT (or a header zt_zlib_decompress rejects with its own message)
+  int code;
+  std::string hmsg;
+  if (zlib_header_status(hs, h, &code, &hmsg)) return set_error(code, hmsg);
   if (!h.fdict) return zt_zlib_decompress(in, n, index, verify, out, out_len, end_ip, adler_out);
   if (dict_len == 0) return set_error(ZT_E_ZLIB_FDICT, "fdict flag is not supported");
   if (hs == ZH_BROKEN) return set_error(ZT_E_INPUT_BROKEN, "input buffer is broken");

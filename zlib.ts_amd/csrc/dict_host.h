@@ -1,11 +1,15 @@
 // dict_host.h -- host-only arithmetic of the preset-dictionary calls
 // (include/zt_dict.h): which bytes of a dictionary the engines use, where they
-// sit in the match kernel's history, and the RFC 1950 FDICT header.  No device
-// code and no HIP types: tools/dict_host_check.cpp runs it under ASan / UBSan.
+// sit in the match kernel's history, and the checks of the RFC 1950 header
+// (its writer: member_frame.h).  No device code and no HIP types:
+// tools/dict_host_check.cpp runs it under ASan / UBSan.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <string>
+
+#include "../../include/zt.h"
 
 namespace zt {
 
@@ -46,19 +50,6 @@ inline void dict_fill_history(const DictLayout &L, const uint8_t *dict, uint8_t 
 inline size_t dict_window_off(size_t dict_len) { return dict_len > kDictWindow ? dict_len - kDictWindow : 0; }
 inline uint32_t dict_window_len(size_t dict_len) { return dict_len > kDictWindow ? kDictWindow : (uint32_t)dict_len; }
 
-// RFC 1950 header with FDICT: CMF, FLG (FLEVEL in bits 6-7, FDICT 0x20, FCHECK
-// so that CMF * 256 + FLG is a multiple of 31), DICTID big-endian
-inline void zlib_dict_header(uint32_t cmf, uint32_t flevel, uint32_t dictid, uint8_t hd[6]) {
-  const uint32_t flg0 = ((flevel & 3u) << 6) | 0x20u;
-  const uint32_t rem = ((cmf << 8) + flg0) % 31;
-  hd[0] = (uint8_t)cmf;
-  hd[1] = (uint8_t)(flg0 | (rem ? 31 - rem : 0));
-  hd[2] = (uint8_t)(dictid >> 24);
-  hd[3] = (uint8_t)(dictid >> 16);
-  hd[4] = (uint8_t)(dictid >> 8);
-  hd[5] = (uint8_t)dictid;
-}
-
 // Header of the zlib stream at in[index ..): the checks of src/Inflate.ts:44-58
 // in their order, then DICTID when FDICT is set.
 enum ZlibHdr {
@@ -94,6 +85,17 @@ inline ZlibHdr zlib_parse_header(const uint8_t *in, size_t n, size_t index, Zlib
     h->body = index + 6;
   }
   return ZH_OK;
+}
+// The reference's status and message for the three header results (true: the
+// header is refused).  What follows -- FDICT without a dictionary, ZH_BROKEN,
+// the dictionary id -- is each caller's own, in its own order.
+inline bool zlib_header_status(ZlibHdr hs, const ZlibHeader &h, int *code, std::string *msg) {
+  if (hs != ZH_METHOD && hs != ZH_FCHECK_NAN && hs != ZH_FCHECK) return false;
+  *code = hs == ZH_METHOD ? ZT_E_ZLIB_METHOD : ZT_E_ZLIB_FCHECK;
+  *msg = hs == ZH_METHOD       ? "unsupported compression method"
+         : hs == ZH_FCHECK_NAN ? "invalid fcheck flag:NaN"
+                               : "invalid fcheck flag:" + std::to_string(h.fcheck);
+  return true;
 }
 
 }  // namespace zt

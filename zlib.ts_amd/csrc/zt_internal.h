@@ -242,9 +242,9 @@ void host_pool_drop();  // the pool's free buffers released (zt_release_scratch)
 // released by zt_free; reserve >= 1 byte per item so every pointer is
 // distinct).  slab_release: true when p lay in a slab (and was released).
 uint8_t *slab_out(size_t total, size_t items, bool pool = false);
-// device framing of batch members (synth.hip): item k's prefix | body |
-// trailer at out + it[k].out_off; trailer 8 = gzip (CRC-32 LE, ISIZE LE),
-// 4 = zlib (Adler-32 BE), 0 = none; sums = (crc, adler) per item
+// device framing of batch members (member_frame.hip): item k's prefix | body |
+// trailer at out + it[k].out_off; the trailer is put_trailer's for `kind`
+// (member_frame.h); sums = (crc, adler) per item
 struct FrameItem {
   uint64_t body_off;  // in the deflate output
   uint64_t out_off;   // in the framed output
@@ -254,7 +254,7 @@ struct FrameItem {
 // patch > 0 (BGZF's BSIZE, bgzf_api.hip): prefix bytes [patch, patch + 2) of
 // item k become its size - 1 (prefix + body + trailer), little endian
 int frame_members_dev(const FrameItem *d_items, uint32_t count, const uint8_t *d_prefix, uint32_t plen,
-                      uint32_t trailer, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s,
+                      MemberKind kind, const uint8_t *d_body, const uint32_t *d_sums, uint8_t *d_out, hipStream_t s,
                       uint32_t patch = 0);
 bool slab_release(void *p);
 // fn(0 .. count-1) over a few host threads when total_bytes is large.
@@ -486,7 +486,6 @@ int checksums_dev(DeviceCtx *c, const uint8_t *d_in, size_t n, bool do_crc, bool
                   uint32_t adler_in, uint32_t *d_result /* [2] */, hipStream_t s);
 int checksums_batch_dev(DeviceCtx *c, const uint8_t *frame, size_t count, const uint64_t *off, const uint64_t *len,
                         uint32_t *d_result /* [2 count] */, hipStream_t s);
-void gzip_header(const zt_gzip_opts *opts, std::vector<uint8_t> &hd);  // container_api.cpp
 int current_device();                                                 // this thread's (zt_set_device)
 std::vector<int> batch_devices();                                     // zt_set_devices, else {current}
 // debug (deflate.hip; exported, not part of include/zt.h): blocks of the
@@ -562,15 +561,27 @@ struct DictHist {
 int deflate_batch_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t count, const uint64_t *off, const uint64_t *len,
                           int ctype, int level, uint8_t *d_out, uint64_t *out_off, void *scratch_base,
                           size_t scratch_size, hipStream_t s, const DictHist *dict = nullptr);
+// The compute step of every member writer: with d_sums, checksums_batch_dev
+// over the packed input on c->aux, forked behind `landed` (null: behind what
+// c->stream holds now) and c->aux_ev recorded on c->aux behind it; with a
+// compressing ctype, deflate_batch_dev_run on c->stream.  join_sums: c->stream
+// waits for those sums (the trailers need them).
+int deflate_members_dev(DeviceCtx *c, const uint8_t *d_in, size_t count, const uint64_t *off, const uint64_t *len,
+                        int ctype, int level, uint8_t *d_body, uint64_t *out_off, void *scratch_base,
+                        size_t scratch_size, const DictHist *dict, uint32_t *d_sums, hipEvent_t landed);
+inline int join_sums(DeviceCtx *c) {
+  ZT_HIP(hipStreamWaitEvent(c->stream, c->aux_ev, 0));
+  return ZT_OK;
+}
 // host dictionary (dict_api.cpp / batch_api.cpp): the batch deflate calls with
-// one dictionary for every buffer (dict_len == 0: none); zlib = FDICT framing
-// with this DICTID
+// one dictionary for every buffer (dict_len == 0: none), framed as `fr`
+// (frame_raw, or frame_zlib_dict with the dictionary's Adler-32)
 struct HostDict {
   const uint8_t *dict = nullptr;
   size_t dict_len = 0;
 };
 int deflate_batch_host(const uint8_t *const *in, const size_t *n, size_t count, const zt_deflate_opts *opts,
-                       const HostDict &hd, bool zlib, uint32_t dictid, uint8_t **out, size_t *out_len, int *status);
+                       const HostDict &hd, const MemberFrame &fr, uint8_t **out, size_t *out_len, int *status);
 // host streams decoded by one wave each with `hist_len` <= 32768 bytes of
 // device history d_hist in front of every stream (inflate_api.cpp)
 int inflate_host_batch_hist(const uint8_t *const *in, const size_t *n, const size_t *index, size_t count,
@@ -607,8 +618,8 @@ struct DevSink {
   // be overwritten by whatever s runs next
   std::function<int(const uint8_t *d_base, const std::vector<SinkPiece> &pieces, hipStream_t s)> put;
 };
-// dev_batch.hip: the copy jobs' tiles (dev_batch_plan.h) and the patch jobs,
-// tables on the device
+// the copy jobs' tiles (dev_batch.hip) and the patch jobs (member_frame.hip),
+// tables (dev_batch_plan.h) on the device
 int dev_copy_dev(const DevCopyJob *d_jobs, uint32_t njobs, uint64_t tiles, hipStream_t s);
 int dev_patch_dev(const DevPatchJob *d_jobs, uint32_t njobs, const uint32_t *d_sums, hipStream_t s);
 // Decode `count` device-resident streams (stream i at d_in + in_off[i],
