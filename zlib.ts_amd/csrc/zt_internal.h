@@ -100,6 +100,8 @@ enum ScratchSlot : int {
   kCkptWin = 33,    // checkpoint build (ckpt_api.hip): window offsets | window records; after the general decode, inside the call
   kDevBatch = 34,   // device-resident batch calls (dev_batch_api.cpp): the copy and patch job tables of one launch;
                     // the holder calls the batch deflate / inflate and checksum launchers (none asks for it)
+  kSession = 35,    // inflate sessions (stream_api.cpp): the job and result records of one launch; the holder
+                    // calls the checksum launcher (it also takes kIn, kOut and kSums for the whole call)
   kScratchSlots
 };
 // Pinned host staging (DeviceCtx::h_pinned, pinned()).

@@ -3,6 +3,7 @@ export { RawDeflate, CompressionType } from './RawDeflate.js';
 export { RawInflate, BufferType } from './RawInflate.js';
 export { RawInflateStream } from './RawInflateStream.js';
 export { InflateStream } from './InflateStream.js';
+export { RawInflateSession } from './InflateSession.js';
 export { CRC32 } from './CRC32.js';
 export { Adler32 } from './Adler32.js';
 export { GZip, GZipFlagsMask, GZipMagicNumber, GZipOperatingSystem } from './GZip.js';

@@ -18,6 +18,7 @@
 #include "../../include/zt_index.h"
 #include "../../include/zt_checkpoint.h"
 #include "../../include/zt_bgzf.h"
+#include "../../include/zt_stream.h"
 
 namespace {
 
@@ -895,6 +896,169 @@ napi_value bgzf_read_virtual(napi_env env, napi_callback_info info) {
   return ranges_result(env, rc, out, olen);
 }
 
+// ---- inflate sessions (include/zt_stream.h) -----------------------------------
+// A session travels through JS as an external value; its finalizer destroys
+// the session unless sessionDestroy already has.
+struct SessionBox {
+  zt_inflate_session *s;
+};
+
+void session_finalize(napi_env, void *data, void *) {
+  SessionBox *b = static_cast<SessionBox *>(data);
+  zt_inflate_session_destroy(b->s);
+  delete b;
+}
+
+SessionBox *get_session(napi_env env, napi_value v) {
+  napi_valuetype t;
+  napi_typeof(env, v, &t);
+  void *data = nullptr;
+  if (t == napi_external) napi_get_value_external(env, v, &data);
+  SessionBox *b = static_cast<SessionBox *>(data);
+  if (!b || !b->s) {
+    napi_throw_type_error(env, nullptr, "expected an open inflate session");
+    return nullptr;
+  }
+  return b;
+}
+
+// sessionCreate([window: Uint8Array]) -> session
+napi_value session_create(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  const uint8_t *w;
+  size_t wn;
+  bool given;
+  if (!opt_u8(env, a[0], &w, &wn, &given)) return nullptr;
+  zt_inflate_session *s = nullptr;
+  const int rc = zt_inflate_session_create(w, wn, &s);
+  if (rc) return throw_zt(env, rc);
+  SessionBox *b = new SessionBox{s};
+  napi_value ext;
+  if (napi_create_external(env, b, session_finalize, nullptr, &ext) != napi_ok) {
+    session_finalize(env, b, nullptr);
+    return nullptr;
+  }
+  return ext;
+}
+
+// sessionFeed(session, chunk: Uint8Array, last) -> Uint8Array (this call's output)
+napi_value session_feed(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  SessionBox *b = get_session(env, a[0]);
+  const uint8_t *p;
+  size_t n;
+  if (!b || !get_u8(env, a[1], &p, &n)) return nullptr;
+  uint8_t *out = nullptr;
+  size_t olen = 0;
+  const int rc = zt_inflate_session_feed(b->s, p, n, get_i64(env, a[2], 0) != 0, &out, &olen);
+  if (rc) return throw_zt(env, rc);
+  return new_u8(env, out, olen);
+}
+
+// sessionsFeed(sessions[], chunks: Uint8Array[], last: boolean | boolean[]) -> [{output} | {status, message}]
+napi_value sessions_feed(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  std::vector<const uint8_t *> in;
+  std::vector<size_t> n;
+  if (!get_u8_array(env, a[1], in, n)) return nullptr;
+  const size_t cnt = in.size();
+  bool is_arr = false;
+  napi_is_array(env, a[0], &is_arr);
+  uint32_t ns = 0;
+  if (is_arr) napi_get_array_length(env, a[0], &ns);
+  if (!is_arr || ns != cnt) {
+    napi_throw_type_error(env, nullptr, "expected one session per chunk");
+    return nullptr;
+  }
+  std::vector<zt_inflate_session *> ss(cnt);
+  std::vector<int> last(cnt, 0);
+  bool last_arr = false;
+  napi_is_array(env, a[2], &last_arr);
+  for (uint32_t i = 0; i < cnt; ++i) {
+    napi_value e;
+    napi_get_element(env, a[0], i, &e);
+    SessionBox *b = get_session(env, e);
+    if (!b) return nullptr;
+    ss[i] = b->s;
+    napi_value f = a[2];
+    if (last_arr) napi_get_element(env, a[2], i, &f);
+    bool flag = false;
+    napi_coerce_to_bool(env, f, &f);
+    napi_get_value_bool(env, f, &flag);
+    last[i] = flag;
+  }
+  std::vector<uint8_t *> out(cnt, nullptr);
+  std::vector<size_t> olen(cnt, 0);
+  std::vector<int> st(cnt, 0);
+  const int rc = zt_inflate_sessions_feed(ss.data(), in.data(), n.data(), last.data(), cnt, out.data(), olen.data(),
+                                          st.data());
+  bool any = false;
+  for (int x : st) any = any || x != 0;
+  if (rc && !any) return throw_zt(env, rc);
+  napi_value arr;
+  napi_create_array_with_length(env, cnt, &arr);
+  for (size_t i = 0; i < cnt; ++i) {
+    napi_value e, m;
+    napi_create_object(env, &e);
+    if (st[i]) {
+      set_num(env, e, "status", st[i]);
+      napi_create_string_utf8(env, zt_inflate_session_message(ss[i]), NAPI_AUTO_LENGTH, &m);
+      napi_set_named_property(env, e, "message", m);
+      zt_free(out[i]);
+    } else {
+      napi_set_named_property(env, e, "output", new_u8(env, out[i], olen[i]));
+    }
+    napi_set_element(env, arr, (uint32_t)i, e);
+  }
+  return arr;
+}
+
+// sessionInfo(session) -> {totalIn, endBits, totalOut, decodedBits, crc32, adler32, pending, finished, status,
+// launches, message}
+napi_value session_info(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  SessionBox *b = get_session(env, a[0]);
+  if (!b) return nullptr;
+  zt_inflate_session_info i;
+  const int rc = zt_inflate_session_get_info(b->s, &i);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj, f, m;
+  napi_create_object(env, &obj);
+  set_num(env, obj, "totalIn", (double)i.total_in);
+  set_num(env, obj, "endBits", (double)i.end_bits);
+  set_num(env, obj, "totalOut", (double)i.total_out);
+  set_num(env, obj, "decodedBits", (double)i.decoded_bits);
+  set_num(env, obj, "crc32", (double)i.crc32);
+  set_num(env, obj, "adler32", (double)i.adler32);
+  set_num(env, obj, "pending", (double)i.pending);
+  set_num(env, obj, "status", (double)i.status);
+  set_num(env, obj, "launches", (double)i.launches);
+  napi_get_boolean(env, i.finished != 0, &f);
+  napi_set_named_property(env, obj, "finished", f);
+  napi_create_string_utf8(env, zt_inflate_session_message(b->s), NAPI_AUTO_LENGTH, &m);
+  napi_set_named_property(env, obj, "message", m);
+  return obj;
+}
+
+// sessionDestroy(session): releases the session now (the finalizer then finds nothing)
+napi_value session_destroy(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  const napi_value undef = args(env, info, a, 1);
+  napi_valuetype t;
+  napi_typeof(env, a[0], &t);
+  void *data = nullptr;
+  if (t == napi_external) napi_get_value_external(env, a[0], &data);
+  if (SessionBox *b = static_cast<SessionBox *>(data)) {
+    zt_inflate_session_destroy(b->s);
+    b->s = nullptr;
+  }
+  return undef;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   napi_value r;
   napi_create_int32(env, zt_device_count(), &r);
@@ -934,6 +1098,11 @@ napi_value init(napi_env env, napi_value exports) {
       {"bgzfDecompress", nullptr, bgzf_decompress, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"bgzfReadRanges", nullptr, bgzf_read_ranges, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"bgzfReadVirtual", nullptr, bgzf_read_virtual, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"sessionCreate", nullptr, session_create, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"sessionFeed", nullptr, session_feed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"sessionsFeed", nullptr, sessions_feed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"sessionInfo", nullptr, session_info, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"sessionDestroy", nullptr, session_destroy, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
   };

@@ -112,6 +112,13 @@ class BgzfStats(ctypes.Structure):
                                                "out_bytes_decoded", "out_bytes_returned")]
 
 
+class InflateSessionInfo(ctypes.Structure):
+    _fields_ = [("total_in", ctypes.c_uint64), ("end_bits", ctypes.c_uint64), ("total_out", ctypes.c_uint64),
+                ("decoded_bits", ctypes.c_uint64), ("crc32", ctypes.c_uint32), ("adler32", ctypes.c_uint32),
+                ("pending", ctypes.c_uint32), ("finished", ctypes.c_int32), ("status", ctypes.c_int32),
+                ("launches", ctypes.c_uint32)]
+
+
 def _load():
     # torch (when present) ships its own libamdhip64.so.7; loading it first makes
     # libzt.so bind to that same runtime (same SONAME) instead of starting a
@@ -233,6 +240,14 @@ def _load():
         "zt_inflate_dev_batch": ([P(vp), P(sz), P(sz), sz, P(vp), P(sz), P(sz), P(sz), P(ctypes.c_int), P(u32),
                                   P(u32), vp], ctypes.c_int),
         "zt_debug_dev_batch_times": ([ctypes.c_int, P(ctypes.c_double)], ctypes.c_int),  # debug (dev_batch_api.cpp)
+        # include/zt_stream.h
+        "zt_inflate_session_create": ([vp, sz, P(vp)], ctypes.c_int),
+        "zt_inflate_session_destroy": ([vp], None),
+        "zt_inflate_session_feed": ([vp, vp, sz, ctypes.c_int, u8pp, P(sz)], ctypes.c_int),
+        "zt_inflate_sessions_feed": ([P(vp), P(vp), P(sz), P(ctypes.c_int), sz, u8pp, P(sz), P(ctypes.c_int)],
+                                     ctypes.c_int),
+        "zt_inflate_session_get_info": ([vp, P(InflateSessionInfo)], ctypes.c_int),
+        "zt_inflate_session_message": ([vp], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -306,6 +321,13 @@ BGZF_SYMBOLS = [
 # every symbol include/zt_dev_batch.h declares (checked by tests/test_dev_batch_host.py)
 DEV_BATCH_SYMBOLS = [
     "zt_deflate_dev_batch", "zt_deflate_dev_batch_bound", "zt_inflate_dev_batch",
+]
+
+
+# every symbol include/zt_stream.h declares (checked by tests/test_stream_host.py)
+STREAM_SYMBOLS = [
+    "zt_inflate_session_create", "zt_inflate_session_destroy", "zt_inflate_session_feed",
+    "zt_inflate_sessions_feed", "zt_inflate_session_get_info", "zt_inflate_session_message",
 ]
 
 
@@ -445,6 +467,98 @@ class RawInflateStream:
         self.total += len(out)
         self.window = (self.window + out)[-32768:]
         return out
+
+
+class InflateSession:
+    """An inflate session (include/zt_stream.h): raw inflate fed piece by
+    piece, only the new bytes each time, resumed at a token; its state stays
+    on the device.  ``feed(data, last)`` returns the bytes this piece
+    completes; ``window`` is a preset dictionary."""
+
+    def __init__(self, window=b""):
+        self._h = ctypes.c_void_p()
+        w, wn = _cbuf(window)
+        _check(lib.zt_inflate_session_create(w, wn, ctypes.byref(self._h)))
+
+    def feed(self, data, last=False):
+        b, n = _cbuf(data)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        olen = ctypes.c_size_t()
+        _check(lib.zt_inflate_session_feed(self._handle(), b, n, int(bool(last)), ctypes.byref(out),
+                                           ctypes.byref(olen)))
+        return _take(out, olen) if out else b""
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the session is closed")
+        return self._h
+
+    def info(self):
+        i = InflateSessionInfo()
+        _check(lib.zt_inflate_session_get_info(self._handle(), ctypes.byref(i)))
+        d = {k: getattr(i, k) for k, _ in InflateSessionInfo._fields_}
+        d["message"] = lib.zt_inflate_session_message(self._h).decode(errors="replace")
+        return d
+
+    @property
+    def finished(self):
+        return bool(self.info()["finished"])
+
+    @property
+    def unused(self):
+        """Fed bytes behind the stream's end (a container's trailer)."""
+        i = self.info()
+        return i["total_in"] - (i["end_bits"] + 7) // 8
+
+    @property
+    def crc32(self):
+        return self.info()["crc32"]
+
+    @property
+    def adler32(self):
+        return self.info()["adler32"]
+
+    def close(self):
+        if self._h:
+            lib.zt_inflate_session_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def inflate_sessions_feed(sessions, chunks, last=False, return_code=False):
+    """zt_inflate_sessions_feed: chunk i fed to session i, all in one call
+    (one wavefront per session).  last: one flag, or one per session.
+    Returns a list of (status, output): status a BatchStatus (0, or the
+    session's sticky error with its message); a failed item has output b"".
+    return_code: also the call's return code, as (code, list)."""
+    k = len(sessions)
+    bs, ptrs, lens = _batch_ptrs(chunks)
+    if len(bs) != k:
+        raise ValueError("one chunk per session")
+    hs = (ctypes.c_void_p * k)(*[x._handle().value for x in sessions])
+    flags = list(last) if isinstance(last, (list, tuple)) else [last] * k
+    fl = (ctypes.c_int * k)(*[int(bool(f)) for f in flags])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_inflate_sessions_feed(hs, ptrs, lens, fl, k, outs, olens, st)
+    if rc != ZT_OK and all(x == 0 for x in st):
+        _check(rc)
+    data = _batch_take(k, outs, olens)
+    res = [(BatchStatus(st[i], lib.zt_inflate_session_message(hs[i]).decode(errors="replace") if st[i] else ""),
+            data[i] if st[i] == 0 else b"") for i in range(k)]
+    return (rc, res) if return_code else res
 
 
 def inflate_raw_batch(streams, ref_strict=False, dictionary=None):
