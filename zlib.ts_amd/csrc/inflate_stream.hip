@@ -17,6 +17,13 @@
 // token boundary or at the start of the block header that did not complete (a
 // partial dynamic header is read again from its start: below 1 KiB).
 //
+// A second reader of the record: cs_truncation (container_stream_host.h)
+// walks a final feed's tokens on the host from the record's phase, bfinal,
+// btype, stored_left, hlit, hdist and lens, as step 1 and step 2 below read
+// them, after a container session's launch ran out of input.  A change to
+// what those fields mean, or to SessRec's layout behind the ring
+// (stream_api.cpp reads lens .. hdist in one copy), has to be made there too.
+//
 // Phantom bits: the Reader of inflate_common.h reads the bits past the end of
 // the input as zeros, and a token can "decode" from them.  So nothing is
 // written to the ring before the whole token -- code, extra bits, distance

@@ -14,29 +14,26 @@
 // (checksums_batch_dev) and combined with the running values on the host, and
 // one download brings them into a slab: the call's own when one round did it
 // all, else the pieces of the rounds move into one.
+//
+// The same loop serves the container sessions (stream_session.h): a session
+// with a frame is walked over its header and trailer bytes on the host
+// (cs_step, container_stream_host.h) before its first launch and after every
+// launch that ended a body; one that starts a new member has its record turned
+// over (session_turn.hip, one launch per round) and is launched again on the
+// rest of its slot.
 #include <cstring>
 #include <map>
 #include <mutex>
 
 #include "../../include/zt_stream.h"
 #include "stream_host.h"
+#include "stream_session.h"
 #include "zt_internal.h"
-
-struct zt_inflate_session {
-  int device = -1;
-  zt::SessRec *d_rec = nullptr;
-  std::vector<uint8_t> pending;  // fed bytes not yet consumed (the first one possibly in part: bit_off)
-  uint32_t bit_off = 0;
-  uint64_t total_in = 0, end_bits = 0, total_out = 0, decoded_bits = 0;
-  uint32_t crc = 0, adler = 1, launches = 0;
-  uint32_t wlen = 0;
-  int finished = 0, status = ZT_OK;
-  std::string msg;
-};
 
 namespace zt {
 
 int session_jobs_dev(const SessJob *d_jobs, SessResult *d_res, int count, hipStream_t s);  // inflate_stream.hip
+int session_turns_dev(const SessTurn *d_turns, int count, hipStream_t s);                  // session_turn.hip
 
 namespace {
 
@@ -82,12 +79,22 @@ int sticky(zt_inflate_session *s, int status, int detail) {
   return s->status;
 }
 
+// a container session's framing error: the frame's own code and text
+int sticky_frame(zt_inflate_session *s) {
+  s->status = s->frame->code;
+  s->msg = s->frame->msg;
+  s->pending.clear();
+  s->pending.shrink_to_fit();
+  return s->status;
+}
+
 // one job of a feed call: item `item`, its slot in the packed input
 struct Item {
   size_t item;
   size_t m;        // pending + new bytes
   size_t used = 0; // bytes of the slot the earlier launches of this call consumed
   unsigned relaunch = 0;
+  bool window = false;  // a container session's preset window goes up before its next launch
   uint64_t out_len = 0;
   uint32_t crc = 0, adler = 1;
   // its output so far: `len` bytes at `off` of round buffer `buf`, in order
@@ -107,8 +114,10 @@ void rounds_release(std::vector<RoundBuf> &rounds) {
   rounds.clear();
 }
 
-int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const *in, const size_t *n, const int *last,
-              size_t count, uint8_t **out, size_t *out_len, int *status) {
+}  // namespace
+
+int sessions_feed_rounds(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const *in, const size_t *n,
+                         const int *last, size_t count, uint8_t **out, size_t *out_len, int *status) {
   hipStream_t s = c->stream;
   std::vector<Item> items;
   for (size_t i = 0; i < count; ++i) {
@@ -121,10 +130,14 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
       continue;
     }
     z->total_in += n[i];
-    if (z->finished) continue;  // trailing bytes: counted only
+    if (z->finished) {  // trailing bytes: counted only
+      if (z->frame) z->frame->unused += n[i];
+      continue;
+    }
     const int fin = last ? last[i] : 0;
     const size_t m = z->pending.size() + n[i];
-    if (!sess_has_work(m, z->bit_off, fin)) {
+    // (a container session outside a body: its frame decides, below)
+    if ((!z->frame || z->frame->state == CS_BODY) && !sess_has_work(m, z->bit_off, fin)) {
       if (n[i]) z->pending.insert(z->pending.end(), in[i], in[i] + n[i]);
       continue;
     }
@@ -150,7 +163,58 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
     if (!z->pending.empty()) memcpy(dst, z->pending.data(), z->pending.size());
     if (n[items[k].item]) memcpy(dst + z->pending.size(), in[items[k].item], n[items[k].item]);
   }
-  ZT_HIP(hipMemcpyAsync(d_in_v, stage, L.total, hipMemcpyHostToDevice, s));
+
+  // ---- container sessions: the frame bytes in front of a body.  advance(k):
+  // item k, outside a body, walks on over its slot; true when a body with
+  // something to decode follows.  The records to turn over collect in `turns`.
+  std::vector<SessTurn> turns;
+  auto advance = [&](size_t k) -> bool {
+    Item &it = items[k];
+    zt_inflate_session *z = ss[it.item];
+    CsFrame *f = z->frame;
+    const int fin = last ? last[it.item] : 0;
+    if (f->state != CS_BODY) {
+      const CsStep st = cs_step(f, stage + L.off[k] + it.used, it.m - it.used, fin, z->total_in - it.m + it.used);
+      it.used += st.consumed;
+      if (st.action == CS_ACT_ERROR) {
+        status[it.item] = sticky_frame(z);
+        return false;
+      }
+      if (st.action == CS_ACT_DONE) {
+        z->finished = 1;
+        f->unused += it.m - it.used;
+        it.used = it.m;
+        return false;
+      }
+      if (st.action == CS_ACT_WAIT) return false;
+      if (st.turn) {
+        it.window = st.window;
+        turns.push_back(SessTurn{z->d_rec, st.op});
+      }
+    }
+    return sess_has_work(it.m - it.used, z->bit_off, fin);
+  };
+  // the records of `turns`: preset windows first, then one turn-over launch
+  auto turn_over = [&]() -> int {
+    if (turns.empty()) return ZT_OK;
+    void *d_turns;
+    ZT_TRY(scratch(c, kSmall, turns.size() * sizeof(SessTurn), &d_turns));
+    for (Item &it : items) {
+      if (!it.window) continue;
+      it.window = false;
+      const zt_inflate_session *z = ss[it.item];
+      ZT_HIP(hipMemcpyAsync(z->d_rec->ring, z->window, z->wlen, hipMemcpyHostToDevice, s));
+    }
+    ZT_HIP(hipMemcpyAsync(d_turns, turns.data(), turns.size() * sizeof(SessTurn), hipMemcpyHostToDevice, s));
+    ZT_TRY(session_turns_dev(static_cast<const SessTurn *>(d_turns), (int)turns.size(), s));
+    ZT_HIP(hipStreamSynchronize(s));  // (`turns` is pageable host memory)
+    turns.clear();
+    return ZT_OK;
+  };
+  std::vector<size_t> active;
+  for (size_t k = 0; k < items.size(); ++k)
+    if (!ss[items[k].item]->frame || advance(k)) active.push_back(k);
+  if (!active.empty()) ZT_HIP(hipMemcpyAsync(d_in_v, stage, L.total, hipMemcpyHostToDevice, s));
 
   // ---- rounds: launch, read the results back, launch again what stopped on a full slot
   std::vector<RoundBuf> rounds;
@@ -158,7 +222,6 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
     std::vector<RoundBuf> &r;
     ~Guard() { rounds_release(r); }
   } guard{rounds};
-  std::vector<size_t> active = ids;
   std::vector<SessJob> jobs;
   std::vector<SessResult> res;
   while (!active.empty()) {
@@ -180,6 +243,7 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
       d_copy = cv.take<DevCopyJob>(na);
       return cv.bytes();
     }));
+    ZT_TRY(turn_over());  // the members that start in this round
     // the slots, and behind them room for their dense copy (an output is
     // shorter than its slot by the slot's 256 bytes of slack)
     void *d_out_v, *d_sums_v;
@@ -236,10 +300,38 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
         it.crc = crc_combine(it.crc, sums[2 * q], ck_len[q]);
         it.adler = adler_combine(it.adler, sums[2 * q + 1], ck_len[q]);
         it.out_len += ck_len[q];
+        if (CsFrame *f = ss[it.item]->frame) {  // the member's own running checksums
+          f->crc = crc_combine(f->crc, sums[2 * q], ck_len[q]);
+          f->adler = adler_combine(f->adler, sums[2 * q + 1], ck_len[q]);
+          f->member_out += ck_len[q];
+        }
         it.pieces.push_back(Item::Piece{rounds.size() - 1, (size_t)ck_off[q], (size_t)ck_len[q]});
       }
     }
 
+    // container sessions whose final feed ran out of input: their records' states, one wait for all
+    // (cs_truncation, container_stream_host.h, walks on from them; session_kernel keeps SessRec's meaning)
+    struct RecState {
+      uint8_t lens[320];
+      uint64_t op;
+      uint32_t phase, bfinal, btype, stored_left, hlit, hdist;
+    };
+    static_assert(offsetof(SessRec, hdist) + 4 - offsetof(SessRec, lens) == sizeof(RecState), "the record's state");
+    std::vector<size_t> rec_state_of(na, 0);
+    size_t broken = 0;
+    for (size_t a = 0; a < na; ++a)
+      if (res[a].stop == SS_ERROR && res[a].status == ZT_E_INPUT_BROKEN && ss[items[active[a]].item]->frame)
+        rec_state_of[a] = broken++;
+    std::vector<RecState> rec_states(broken);
+    if (broken) {
+      for (size_t a = 0; a < na; ++a) {
+        const zt_inflate_session *z = ss[items[active[a]].item];
+        if (res[a].stop == SS_ERROR && res[a].status == ZT_E_INPUT_BROKEN && z->frame)
+          ZT_HIP(hipMemcpyAsync(&rec_states[rec_state_of[a]], z->d_rec->lens, sizeof(RecState), hipMemcpyDeviceToHost,
+                                s));
+      }
+      ZT_HIP(hipStreamSynchronize(s));
+    }
     std::vector<int32_t> stops(na);
     for (size_t a = 0; a < na; ++a) {
       Item &it = items[active[a]];
@@ -249,7 +341,18 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
       z->decoded_bits += r.read_bits;
       stops[a] = r.stop;
       if (r.stop == SS_ERROR) {
-        status[it.item] = sticky(z, r.status, r.detail);
+        int code = r.status;
+        if (z->frame && code == ZT_E_INPUT_BROKEN) {
+          // a container session reports the one-shot call's status: where did the input end?
+          // (the record is what it was before this launch; z->bit_off too)
+          const RecState &st = rec_states[rec_state_of[a]];
+          const CsTruncation t = cs_truncation(stage + L.off[active[a]] + it.used, it.m - it.used, z->bit_off,
+                                               st.phase, st.bfinal, st.btype, st.stored_left, st.hlit, st.hdist,
+                                               st.lens);
+          if (t == CS_TRUNC_STORED_LEN) code = ZT_E_STORED_LEN;
+          if (t == CS_TRUNC_STORED_NLEN) code = ZT_E_STORED_NLEN;
+        }
+        status[it.item] = sticky(z, code, r.detail);
         continue;
       }
       // the slot's front the decoded tokens consumed
@@ -257,21 +360,41 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
       z->end_bits += r.end_bits - z->bit_off;
       z->bit_off = t.bit_off;
       it.used += t.drop;
-      if (r.stop == SS_FINISHED) z->finished = 1;
+      if (r.stop == SS_FINISHED && !z->frame) z->finished = 1;
       if (r.stop == SS_OUT_FULL) it.relaunch++;
     }
+    // the next round: what stopped on a full slot, and the container sessions
+    // whose body ended with the next member's body inside the slot
+    std::vector<char> again(na, 0);
+    for (const size_t a : sess_relaunch(stops)) again[a] = 1;
+    for (size_t a = 0; a < na; ++a) {
+      Item &it = items[active[a]];
+      zt_inflate_session *z = ss[it.item];
+      if (stops[a] != SS_FINISHED || !z->frame) continue;
+      if (z->bit_off) {  // the trailer starts at the next whole byte
+        it.used++;
+        z->bit_off = 0;
+      }
+      it.relaunch = 0;
+      z->frame->state = CS_TRAILER;
+      again[a] = advance(active[a]);
+    }
     std::vector<size_t> next;
-    for (const size_t a : sess_relaunch(stops)) next.push_back(active[a]);
+    for (size_t a = 0; a < na; ++a)
+      if (again[a]) next.push_back(active[a]);
     active.swap(next);
   }
+  ZT_TRY(turn_over());  // (a member whose header ended the fed bytes)
 
   // ---- the sessions' books and the outputs.  One round with every item's
   // output kept: its buffer is the call's slab.  Else the pieces move into one.
   bool direct = rounds.size() == 1;
   size_t slab_total = 0, slab_items = 0;
+  // (a failing feed returns nothing; a container session's returns what its earlier launches decoded)
+  auto keeps = [&](const Item &it) { return it.out_len && (!ss[it.item]->status || ss[it.item]->frame); };
   for (const Item &it : items) {
-    if (it.out_len && ss[it.item]->status) direct = false;  // (a failing feed returns nothing)
-    if (!ss[it.item]->status && it.out_len) {
+    if (it.out_len && !keeps(it)) direct = false;
+    if (keeps(it)) {
       slab_total += align_up((size_t)it.out_len, 64);
       slab_items++;
     }
@@ -287,13 +410,14 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
   size_t at = 0;
   for (const Item &it : items) {
     zt_inflate_session *z = ss[it.item];
-    if (z->status) continue;
-    const uint8_t *slot = stage + L.off[&it - items.data()];
-    if (z->finished)
-      z->pending.clear();
-    else
-      z->pending.assign(slot + it.used, slot + it.m);
-    if (!it.out_len) continue;
+    if (!z->status) {
+      const uint8_t *slot = stage + L.off[&it - items.data()];
+      if (z->finished)
+        z->pending.clear();
+      else
+        z->pending.assign(slot + it.used, slot + it.m);
+    }
+    if (!keeps(it)) continue;
     size_t w = 0;
     uint8_t *dst;
     if (direct) {
@@ -316,7 +440,27 @@ int feed_impl(DeviceCtx *c, zt_inflate_session *const *ss, const uint8_t *const 
   return ZT_OK;
 }
 
-}  // namespace
+// a record whose state is "at the start of a stream with this preset window"
+int session_record_take(DeviceCtx *c, const uint8_t *window, size_t wlen, SessRec **out) {
+  SessRec *rec;
+  ZT_TRY(rec_take(c->device, &rec));
+  // the record's state: everything behind the ring zero but the cursor
+  static_assert(offsetof(SessRec, lens) == kSessRing, "state follows the ring");
+  std::vector<uint8_t> st(sizeof(SessRec) - kSessRing, 0);
+  const uint64_t op = wlen;
+  memcpy(st.data() + (offsetof(SessRec, op) - kSessRing), &op, sizeof op);
+  hipError_t e = hipMemcpyAsync(rec->lens, st.data(), st.size(), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && wlen) e = hipMemcpyAsync(rec->ring, window, wlen, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    rec_give(c->device, rec);
+    return hip_fail(e, "session record upload");
+  }
+  *out = rec;
+  return ZT_OK;
+}
+void session_record_give(int device, SessRec *rec) { rec_give(device, rec); }
+
 }  // namespace zt
 
 using namespace zt;
@@ -334,19 +478,7 @@ int zt_inflate_session_create(const uint8_t *window, size_t wlen, zt_inflate_ses
   }
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
   SessRec *rec;
-  ZT_TRY(rec_take(c->device, &rec));
-  // the record's state: everything behind the ring zero but the cursor
-  static_assert(offsetof(SessRec, lens) == kSessRing, "state follows the ring");
-  std::vector<uint8_t> st(sizeof(SessRec) - kSessRing, 0);
-  const uint64_t op = wlen;
-  memcpy(st.data() + (offsetof(SessRec, op) - kSessRing), &op, sizeof op);
-  hipError_t e = hipMemcpyAsync(rec->lens, st.data(), st.size(), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && wlen) e = hipMemcpyAsync(rec->ring, window, wlen, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) {
-    rec_give(c->device, rec);
-    return hip_fail(e, "session record upload");
-  }
+  ZT_TRY(session_record_take(c, window, wlen, &rec));
   zt_inflate_session *z = new zt_inflate_session();
   z->device = c->device;
   z->d_rec = rec;
@@ -374,7 +506,7 @@ int zt_inflate_sessions_feed(zt_inflate_session *const *s, const uint8_t *const 
   if (sess_has_duplicates(reinterpret_cast<const void *const *>(s), count))
     return set_error(ZT_E_ARG, "a session is named twice in one call");
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-  const int rc = feed_impl(c, s, in, n, last, count, out, out_len, status);
+  const int rc = sessions_feed_rounds(c, s, in, n, last, count, out, out_len, status);
   if (rc) {  // the call itself failed: no item keeps an output
     for (size_t i = 0; i < count; ++i) {
       zt_free(out[i]);

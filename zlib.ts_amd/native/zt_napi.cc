@@ -19,6 +19,7 @@
 #include "../../include/zt_checkpoint.h"
 #include "../../include/zt_bgzf.h"
 #include "../../include/zt_stream.h"
+#include "../../include/zt_stream_container.h"
 
 namespace {
 
@@ -1059,6 +1060,223 @@ napi_value session_destroy(napi_env env, napi_callback_info info) {
   return undef;
 }
 
+// ---- container sessions (include/zt_stream_container.h) ---------------------------
+struct ContainerBox {
+  zt_container_session *s;
+};
+
+void container_finalize(napi_env, void *data, void *) {
+  ContainerBox *b = static_cast<ContainerBox *>(data);
+  zt_container_session_destroy(b->s);
+  delete b;
+}
+
+ContainerBox *get_container(napi_env env, napi_value v) {
+  napi_valuetype t;
+  napi_typeof(env, v, &t);
+  void *data = nullptr;
+  if (t == napi_external) napi_get_value_external(env, v, &data);
+  ContainerBox *b = static_cast<ContainerBox *>(data);
+  if (!b || !b->s) {
+    napi_throw_type_error(env, nullptr, "expected an open container session");
+    return nullptr;
+  }
+  return b;
+}
+
+// containerSessionCreate(format, [dictionary: Uint8Array], verify) -> session
+napi_value container_session_create(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  const uint8_t *d;
+  size_t dn;
+  bool given;
+  if (!opt_u8(env, a[1], &d, &dn, &given)) return nullptr;
+  zt_container_session *s = nullptr;
+  const int rc = zt_container_session_create((int)get_i64(env, a[0], 0), dn ? d : nullptr, dn,
+                                             get_i64(env, a[2], 1) != 0, &s);
+  if (rc) return throw_zt(env, rc);
+  ContainerBox *b = new ContainerBox{s};
+  napi_value ext;
+  if (napi_create_external(env, b, container_finalize, nullptr, &ext) != napi_ok) {
+    container_finalize(env, b, nullptr);
+    return nullptr;
+  }
+  return ext;
+}
+
+// containerSessionFeed(session, chunk: Uint8Array, last) -> Uint8Array (this call's output); the error it
+// throws carries `output`: the bytes the call decoded before the error
+napi_value container_session_feed(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  ContainerBox *b = get_container(env, a[0]);
+  const uint8_t *p;
+  size_t n;
+  if (!b || !get_u8(env, a[1], &p, &n)) return nullptr;
+  uint8_t *out = nullptr;
+  size_t olen = 0;
+  const int rc = zt_container_session_feed(b->s, p, n, get_i64(env, a[2], 0) != 0, &out, &olen);
+  if (rc) {
+    const char *msg = zt_last_error_message();
+    char codebuf[16];
+    snprintf(codebuf, sizeof codebuf, "%d", rc);
+    napi_value err, m, c, num;
+    napi_create_string_utf8(env, msg ? msg : "libzt error", NAPI_AUTO_LENGTH, &m);
+    napi_create_string_utf8(env, codebuf, NAPI_AUTO_LENGTH, &c);
+    napi_create_error(env, c, m, &err);
+    napi_create_int32(env, rc, &num);
+    napi_set_named_property(env, err, "ztStatus", num);
+    napi_set_named_property(env, err, "output", new_u8(env, out, olen));
+    napi_throw(env, err);
+    return nullptr;
+  }
+  return new_u8(env, out, olen);
+}
+
+// containerSessionsFeed(sessions[], chunks: Uint8Array[], last: boolean | boolean[])
+//   -> [{output} | {status, message, output}]  (a failing item's output: what the call decoded before the error)
+napi_value container_sessions_feed(napi_env env, napi_callback_info info) {
+  napi_value a[3];
+  args(env, info, a, 3);
+  std::vector<const uint8_t *> in;
+  std::vector<size_t> n;
+  if (!get_u8_array(env, a[1], in, n)) return nullptr;
+  const size_t cnt = in.size();
+  bool is_arr = false;
+  napi_is_array(env, a[0], &is_arr);
+  uint32_t ns = 0;
+  if (is_arr) napi_get_array_length(env, a[0], &ns);
+  if (!is_arr || ns != cnt) {
+    napi_throw_type_error(env, nullptr, "expected one session per chunk");
+    return nullptr;
+  }
+  std::vector<zt_container_session *> ss(cnt);
+  std::vector<int> last(cnt, 0);
+  bool last_arr = false;
+  napi_is_array(env, a[2], &last_arr);
+  for (uint32_t i = 0; i < cnt; ++i) {
+    napi_value e;
+    napi_get_element(env, a[0], i, &e);
+    ContainerBox *b = get_container(env, e);
+    if (!b) return nullptr;
+    ss[i] = b->s;
+    napi_value f = a[2];
+    if (last_arr) napi_get_element(env, a[2], i, &f);
+    bool flag = false;
+    napi_coerce_to_bool(env, f, &f);
+    napi_get_value_bool(env, f, &flag);
+    last[i] = flag;
+  }
+  std::vector<uint8_t *> out(cnt, nullptr);
+  std::vector<size_t> olen(cnt, 0);
+  std::vector<int> st(cnt, 0);
+  const int rc = zt_container_sessions_feed(ss.data(), in.data(), n.data(), last.data(), cnt, out.data(), olen.data(),
+                                            st.data());
+  bool any = false;
+  for (int x : st) any = any || x != 0;
+  if (rc && !any) return throw_zt(env, rc);
+  napi_value arr;
+  napi_create_array_with_length(env, cnt, &arr);
+  for (size_t i = 0; i < cnt; ++i) {
+    napi_value e, m;
+    napi_create_object(env, &e);
+    if (st[i]) {
+      set_num(env, e, "status", st[i]);
+      napi_create_string_utf8(env, zt_container_session_message(ss[i]), NAPI_AUTO_LENGTH, &m);
+      napi_set_named_property(env, e, "message", m);
+    }
+    napi_set_named_property(env, e, "output", new_u8(env, out[i], olen[i]));
+    napi_set_element(env, arr, (uint32_t)i, e);
+  }
+  return arr;
+}
+
+// containerSessionInfo(session) -> {totalIn, totalOut, membersDone, unused, decodedBits, endBits, crc32, adler32,
+// atMemberEnd, finished, status, launches, format, pending, message, members: [...]}
+napi_value container_session_info(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  args(env, info, a, 1);
+  ContainerBox *b = get_container(env, a[0]);
+  if (!b) return nullptr;
+  zt_container_session_info i;
+  const int rc = zt_container_session_get_info(b->s, &i);
+  if (rc) return throw_zt(env, rc);
+  napi_value obj, f, m, arr;
+  napi_create_object(env, &obj);
+  set_num(env, obj, "totalIn", (double)i.total_in);
+  set_num(env, obj, "totalOut", (double)i.total_out);
+  set_num(env, obj, "membersDone", (double)i.members_done);
+  set_num(env, obj, "unused", (double)i.unused);
+  set_num(env, obj, "decodedBits", (double)i.decoded_bits);
+  set_num(env, obj, "endBits", (double)i.end_bits);
+  set_num(env, obj, "crc32", (double)i.crc32);
+  set_num(env, obj, "adler32", (double)i.adler32);
+  set_num(env, obj, "status", (double)i.status);
+  set_num(env, obj, "launches", (double)i.launches);
+  set_num(env, obj, "format", (double)i.format);
+  set_num(env, obj, "pending", (double)i.pending);
+  napi_get_boolean(env, i.finished != 0, &f);
+  napi_set_named_property(env, obj, "finished", f);
+  napi_get_boolean(env, i.at_member_end != 0, &f);
+  napi_set_named_property(env, obj, "atMemberEnd", f);
+  napi_create_string_utf8(env, zt_container_session_message(b->s), NAPI_AUTO_LENGTH, &m);
+  napi_set_named_property(env, obj, "message", m);
+  napi_create_array_with_length(env, (size_t)i.members_done, &arr);
+  for (size_t k = 0; k < i.members_done; ++k) {
+    zt_container_member cm;
+    if (zt_container_session_member(b->s, k, &cm)) break;
+    napi_value e;
+    napi_create_object(env, &e);
+    set_num(env, e, "flg", cm.flg);
+    set_num(env, e, "mtime", cm.mtime);
+    set_num(env, e, "xfl", cm.xfl);
+    set_num(env, e, "os", cm.os);
+    set_num(env, e, "xlen", cm.xlen);
+    set_num(env, e, "hasCrc16", cm.has_crc16);
+    set_num(env, e, "crc16", cm.crc16);
+    set_num(env, e, "crc32", cm.crc32);
+    set_num(env, e, "isize", cm.isize);
+    set_num(env, e, "dataOff", (double)cm.data_off);
+    set_num(env, e, "dataLen", (double)cm.data_len);
+    set_num(env, e, "inOff", (double)cm.in_off);
+    for (int which = 0; which < 2; ++which) {
+      const bool has = cm.flg & (which ? 0x10u : 0x08u);
+      const uint8_t *src = which ? cm.comment : cm.name;
+      const size_t len = which ? cm.comment_len : cm.name_len;
+      napi_value v;
+      if (has) {
+        void *dst = nullptr;
+        napi_value ab;
+        napi_create_arraybuffer(env, len, &dst, &ab);
+        if (len) memcpy(dst, src, len);
+        napi_create_typedarray(env, napi_uint8_array, len, ab, 0, &v);
+      } else {
+        napi_get_null(env, &v);
+      }
+      napi_set_named_property(env, e, which ? "comment" : "name", v);
+    }
+    napi_set_element(env, arr, (uint32_t)k, e);
+  }
+  napi_set_named_property(env, obj, "members", arr);
+  return obj;
+}
+
+// containerSessionDestroy(session): releases the session now (the finalizer then finds nothing)
+napi_value container_session_destroy(napi_env env, napi_callback_info info) {
+  napi_value a[1];
+  const napi_value undef = args(env, info, a, 1);
+  napi_valuetype t;
+  napi_typeof(env, a[0], &t);
+  void *data = nullptr;
+  if (t == napi_external) napi_get_value_external(env, a[0], &data);
+  if (ContainerBox *b = static_cast<ContainerBox *>(data)) {
+    zt_container_session_destroy(b->s);
+    b->s = nullptr;
+  }
+  return undef;
+}
+
 napi_value device_count(napi_env env, napi_callback_info) {
   napi_value r;
   napi_create_int32(env, zt_device_count(), &r);
@@ -1103,6 +1321,12 @@ napi_value init(napi_env env, napi_value exports) {
       {"sessionsFeed", nullptr, sessions_feed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"sessionInfo", nullptr, session_info, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"sessionDestroy", nullptr, session_destroy, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"containerSessionCreate", nullptr, container_session_create, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"containerSessionFeed", nullptr, container_session_feed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"containerSessionsFeed", nullptr, container_sessions_feed, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"containerSessionInfo", nullptr, container_session_info, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+      {"containerSessionDestroy", nullptr, container_session_destroy, nullptr, nullptr, nullptr, napi_enumerable,
+       nullptr},
       {"deviceCount", nullptr, device_count, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
       {"version", nullptr, version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
   };

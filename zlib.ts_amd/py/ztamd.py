@@ -119,6 +119,22 @@ class InflateSessionInfo(ctypes.Structure):
                 ("launches", ctypes.c_uint32)]
 
 
+class ContainerSessionInfo(ctypes.Structure):
+    _fields_ = [("total_in", ctypes.c_uint64), ("total_out", ctypes.c_uint64), ("members_done", ctypes.c_uint64),
+                ("unused", ctypes.c_uint64), ("decoded_bits", ctypes.c_uint64), ("end_bits", ctypes.c_uint64),
+                ("crc32", ctypes.c_uint32), ("adler32", ctypes.c_uint32), ("at_member_end", ctypes.c_int32),
+                ("finished", ctypes.c_int32), ("status", ctypes.c_int32), ("launches", ctypes.c_uint32),
+                ("format", ctypes.c_int32), ("pending", ctypes.c_uint32)]
+
+
+class ContainerMember(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_uint32) for f in ("flg", "mtime", "xfl", "os", "xlen", "has_crc16", "crc16", "crc32",
+                                               "isize", "pad")] + [
+        ("name", ctypes.c_void_p), ("name_len", ctypes.c_size_t), ("comment", ctypes.c_void_p),
+        ("comment_len", ctypes.c_size_t), ("data_off", ctypes.c_uint64), ("data_len", ctypes.c_uint64),
+        ("in_off", ctypes.c_uint64)]
+
+
 def _load():
     # torch (when present) ships its own libamdhip64.so.7; loading it first makes
     # libzt.so bind to that same runtime (same SONAME) instead of starting a
@@ -248,6 +264,15 @@ def _load():
                                      ctypes.c_int),
         "zt_inflate_session_get_info": ([vp, P(InflateSessionInfo)], ctypes.c_int),
         "zt_inflate_session_message": ([vp], ctypes.c_char_p),
+        # include/zt_stream_container.h
+        "zt_container_session_create": ([ctypes.c_int, vp, sz, ctypes.c_int, P(vp)], ctypes.c_int),
+        "zt_container_session_destroy": ([vp], None),
+        "zt_container_session_feed": ([vp, vp, sz, ctypes.c_int, u8pp, P(sz)], ctypes.c_int),
+        "zt_container_sessions_feed": ([P(vp), P(vp), P(sz), P(ctypes.c_int), sz, u8pp, P(sz), P(ctypes.c_int)],
+                                       ctypes.c_int),
+        "zt_container_session_get_info": ([vp, P(ContainerSessionInfo)], ctypes.c_int),
+        "zt_container_session_member": ([vp, sz, P(ContainerMember)], ctypes.c_int),
+        "zt_container_session_message": ([vp], ctypes.c_char_p),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -329,6 +354,15 @@ STREAM_SYMBOLS = [
     "zt_inflate_session_create", "zt_inflate_session_destroy", "zt_inflate_session_feed",
     "zt_inflate_sessions_feed", "zt_inflate_session_get_info", "zt_inflate_session_message",
 ]
+
+
+# every symbol include/zt_stream_container.h declares (checked by tests/test_container_stream_host.py)
+CONTAINER_STREAM_SYMBOLS = [
+    "zt_container_session_create", "zt_container_session_destroy", "zt_container_session_feed",
+    "zt_container_sessions_feed", "zt_container_session_get_info", "zt_container_session_member",
+    "zt_container_session_message",
+]
+SESSION_AUTO, SESSION_GZIP, SESSION_ZLIB = 0, 1, 2
 
 
 def _check(rc):
@@ -558,6 +592,123 @@ def inflate_sessions_feed(sessions, chunks, last=False, return_code=False):
     data = _batch_take(k, outs, olens)
     res = [(BatchStatus(st[i], lib.zt_inflate_session_message(hs[i]).decode(errors="replace") if st[i] else ""),
             data[i] if st[i] == 0 else b"") for i in range(k)]
+    return (rc, res) if return_code else res
+
+
+class _ContainerSession:
+    """A container session (include/zt_stream_container.h): a gzip file or a
+    zlib stream fed piece by piece, only the new bytes each time; the bodies
+    are decoded by the inflate sessions' kernel.  ``feed(data, last)`` returns
+    the bytes this piece completes; when it fails, the ZtError's ``output``
+    holds the bytes the call decoded before the error."""
+
+    def __init__(self, fmt, dictionary=None, verify=True):
+        self._h = ctypes.c_void_p()
+        d, dn = _cbuf(dictionary if dictionary is not None else b"")
+        _check(lib.zt_container_session_create(fmt, d if dn else None, dn, int(bool(verify)), ctypes.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise ValueError("the session is closed")
+        return self._h
+
+    def feed(self, data, last=False):
+        b, n = _cbuf(data)
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        olen = ctypes.c_size_t()
+        rc = lib.zt_container_session_feed(self._handle(), b, n, int(bool(last)), ctypes.byref(out),
+                                           ctypes.byref(olen))
+        res = _take(out, olen) if out else b""
+        if rc != ZT_OK:
+            e = ZtError(rc, lib.zt_last_error_message().decode(errors="replace"))
+            e.output = res
+            raise e
+        return res
+
+    def info(self):
+        i = ContainerSessionInfo()
+        _check(lib.zt_container_session_get_info(self._handle(), ctypes.byref(i)))
+        d = {k: getattr(i, k) for k, _ in ContainerSessionInfo._fields_}
+        d["message"] = lib.zt_container_session_message(self._h).decode(errors="replace")
+        return d
+
+    def members(self):
+        """The members whose trailer was checked, as gunzip() gives them (no
+        ``data``: the bytes went out with the feeds; ``data_off`` / ``data_len``
+        place them in the total output, ``in_off`` the member in the input)."""
+        res = []
+        for k in range(self.info()["members_done"]):
+            m = ContainerMember()
+            _check(lib.zt_container_session_member(self._handle(), k, ctypes.byref(m)))
+            d = {f: getattr(m, f) for f, _ in ContainerMember._fields_ if f not in ("pad", "name", "comment")}
+            d["name"] = ctypes.string_at(m.name, m.name_len) if m.flg & 0x08 else None
+            d["comment"] = ctypes.string_at(m.comment, m.comment_len) if m.flg & 0x10 else None
+            res.append(d)
+        return res
+
+    @property
+    def finished(self):
+        return bool(self.info()["finished"])
+
+    @property
+    def unused(self):
+        """zlib: fed bytes behind the Adler-32."""
+        return self.info()["unused"]
+
+    def close(self):
+        if self._h:
+            lib.zt_container_session_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GunzipSession(_ContainerSession):
+    """Streaming gunzip of one gzip file, any number of members."""
+
+    def __init__(self, verify=True, auto=False):
+        super().__init__(SESSION_AUTO if auto else SESSION_GZIP, None, verify)
+
+
+class ZlibInflateSession(_ContainerSession):
+    """Streaming inflate of one zlib stream; dictionary: used when it carries FDICT."""
+
+    def __init__(self, dictionary=None, verify=True, auto=False):
+        super().__init__(SESSION_AUTO if auto else SESSION_ZLIB, dictionary, verify)
+
+
+def container_sessions_feed(sessions, chunks, last=False, return_code=False):
+    """zt_container_sessions_feed: chunk i fed to container session i, all in
+    one call.  last: one flag, or one per session.  Returns a list of (status,
+    output): status a BatchStatus (0, or the session's sticky error with its
+    message); a failed item's output is what the call decoded before the
+    error.  return_code: also the call's return code, as (code, list)."""
+    k = len(sessions)
+    bs, ptrs, lens = _batch_ptrs(chunks)
+    if len(bs) != k:
+        raise ValueError("one chunk per session")
+    hs = (ctypes.c_void_p * k)(*[x._handle().value for x in sessions])
+    flags = list(last) if isinstance(last, (list, tuple)) else [last] * k
+    fl = (ctypes.c_int * k)(*[int(bool(f)) for f in flags])
+    outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
+    olens = (ctypes.c_size_t * k)()
+    st = (ctypes.c_int * k)()
+    rc = lib.zt_container_sessions_feed(hs, ptrs, lens, fl, k, outs, olens, st)
+    if rc != ZT_OK and all(x == 0 for x in st):
+        _check(rc)
+    data = _batch_take(k, outs, olens)
+    res = [(BatchStatus(st[i], lib.zt_container_session_message(hs[i]).decode(errors="replace") if st[i] else ""),
+            data[i]) for i in range(k)]
     return (rc, res) if return_code else res
 
 
