@@ -1782,13 +1782,10 @@ static DeflateParams deflate_params(int level, int ctype, uint32_t nblocks, cons
   return P;
 }
 
-// The pipeline on s: classify -> match (nwg workgroups; D: the _dict kernels)
-// -> deflate_post_run (-> deflate_index_kernel when the call asks for its
-// index entries), then off[first .. nblocks] read back into h_off and the
-// fault check.
-static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off, uint32_t nwg, const DictView *D,
-                            uint32_t first, uint64_t *h_off, hipStream_t s, const DeflateIndexReq *ix = nullptr) {
-  ZT_TRY(timing_begin(c, s, 1));
+// The pipeline's first part on s: classify -> match (nwg workgroups; D: the
+// _dict kernels).  res holds every searched position's match word afterwards
+// (zt_debug_match stops here).
+static int deflate_match_launch(DeviceCtx *c, const DeflateParams &P, uint32_t nwg, const DictView *D, hipStream_t s) {
   ZT_HIP(hipMemsetAsync(P.nstore, 0, 8, s));
   if (P.store) {
     if (D)
@@ -1804,6 +1801,16 @@ static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off,
     match_kernel<<<nwg, DF_THREADS, 0, s>>>(P);
   ZT_HIP(hipGetLastError());
   ZT_TRY(timing_end(c, s, 0));
+  return ZT_OK;
+}
+
+// The pipeline on s: deflate_match_launch -> deflate_post_run (->
+// deflate_index_kernel when the call asks for its index entries), then
+// off[first .. nblocks] read back into h_off and the fault check.
+static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off, uint32_t nwg, const DictView *D,
+                            uint32_t first, uint64_t *h_off, hipStream_t s, const DeflateIndexReq *ix = nullptr) {
+  ZT_TRY(timing_begin(c, s, 1));
+  ZT_TRY(deflate_match_launch(c, P, nwg, D, s));
   ZT_TRY(deflate_post_run(P, off, s));
   ZT_TRY(timing_end(c, s, 1));
   if (ix) ZT_TRY(deflate_index_launch(P, *ix, s));
@@ -1826,6 +1833,35 @@ static int deflate_pipeline(DeviceCtx *c, const DeflateParams &P, uint64_t *off,
   return ZT_OK;
 }
 
+// One stream of n > 0 bytes at d_in (halo bytes of history in front of it) in
+// one pipeline: its scratch, its parameters and its work split (deflate_dev_run
+// and zt_debug_match)
+struct DeflateCall {
+  DeflateScratch S;
+  DeflateParams P;
+  uint32_t nwg;
+};
+
+static int deflate_stream_call(const DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype,
+                               int level, uint8_t *d_out, void *scratch_base, size_t scratch_size, DeflateCall *k) {
+  const uint32_t nblocks = deflate_nblocks(n);
+  const DeflateGeom G = deflate_geometry(c, nblocks);
+  k->S = deflate_scratch(scratch_base, nblocks, false);
+  if (k->S.bytes > scratch_size) return set_error(ZT_E_NOMEM, "deflate scratch too small");
+  DeflateParams &P = k->P;
+  P = deflate_params(level, ctype, nblocks, k->S, d_out);
+  P.base = d_in - halo;
+  P.halo = halo;
+  P.end = halo + n;
+  P.final_ = final_;
+  P.blocks_per_wg = G.k;
+  P.big_wgs = G.big_wgs;
+  P.tail_k = G.tail_k;
+  P.restart = (kRestartBlocks + G.k - 1) / G.k * G.k;
+  k->nwg = G.nwg;
+  return ZT_OK;
+}
+
 int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, int final_, int ctype, int level,
                     uint8_t *d_out, size_t *out_len, void *scratch_base, size_t scratch_size, hipStream_t s,
                     const DeflateIndexReq *ix) {
@@ -1844,21 +1880,10 @@ int deflate_dev_run(DeviceCtx *c, const uint8_t *d_in, size_t n, size_t halo, in
     *out_len = n + 5 * nb;
     return ZT_OK;
   }
-  const uint32_t nblocks = deflate_nblocks(n);
-  const DeflateGeom G = deflate_geometry(c, nblocks);
-  const DeflateScratch S = deflate_scratch(scratch_base, nblocks, false);
-  if (S.bytes > scratch_size) return set_error(ZT_E_NOMEM, "deflate scratch too small");
-  DeflateParams P = deflate_params(level, ctype, nblocks, S, d_out);
-  P.base = d_in - halo;
-  P.halo = halo;
-  P.end = halo + n;
-  P.final_ = final_;
-  P.blocks_per_wg = G.k;
-  P.big_wgs = G.big_wgs;
-  P.tail_k = G.tail_k;
-  P.restart = (kRestartBlocks + G.k - 1) / G.k * G.k;
+  DeflateCall k;
+  ZT_TRY(deflate_stream_call(c, d_in, n, halo, final_, ctype, level, d_out, scratch_base, scratch_size, &k));
   uint64_t total = 0;
-  ZT_TRY(deflate_pipeline(c, P, S.off, G.nwg, nullptr, nblocks, &total, s, ix));
+  ZT_TRY(deflate_pipeline(c, k.P, k.S.off, k.nwg, nullptr, k.P.nblocks, &total, s, ix));
   *out_len = total;
   return ZT_OK;
 }
@@ -1950,6 +1975,41 @@ extern "C" int zt_debug_match_modes(uint64_t out[2]) {
   ZT_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_match_modes), z, sizeof z));
   out[0] = v[0];
   out[1] = v[1];
+  return ZT_OK;
+}
+
+// the match stage's result for one stream (zt_internal.h)
+extern "C" int zt_debug_match(const uint8_t *in, size_t n, size_t halo, int level, uint32_t *res, uint8_t *store,
+                              uint32_t *info) {
+  if (!in || !res || !store || !info || n == 0 || halo > 32768)
+    return set_error(ZT_E_ARG, "zt_debug_match: bad argument");
+  DeviceCtx *c;
+  ZT_TRY(get_ctx(&c));
+  std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+  const zt_deflate_opts opts{2, 0, level};  // DYNAMIC: the blocks are classified
+  int ct, lv;
+  ZT_TRY(resolve_opts(&opts, &ct, &lv));
+  hipStream_t s = c->stream;
+  void *d_in, *d_scr;
+  ZT_TRY(scratch(c, kIn, halo + n + 64, &d_in));
+  const size_t ss = deflate_scratch_bytes(c, n);
+  ZT_TRY(scratch(c, kDeflateOrDesc, ss, &d_scr));
+  ZT_TRY(upload(c, d_in, in, halo + n, s));
+  DeflateCall k;
+  ZT_TRY(deflate_stream_call(c, (const uint8_t *)d_in + halo, n, halo, 1, ct, lv, nullptr, d_scr, ss, &k));
+  const DeflateParams &P = k.P;
+  // (length 511: a position the kernel never wrote stays visible)
+  ZT_HIP(hipMemsetAsync(P.res, 0xFF, (size_t)P.nblocks * DF_BLOCK * 4, s));
+  ZT_TRY(deflate_match_launch(c, P, k.nwg, nullptr, s));
+  ZT_TRY(download(c, res, P.res, n * 4, s));
+  ZT_TRY(download(c, store, k.S.store, P.nblocks, s));
+  const uint32_t rec[kDebugMatchInfo] = {
+      (uint32_t)DF_BLOCK,      (uint32_t)DF_SUB,       (uint32_t)DF_MAXDIST,    P.restart * (uint32_t)DF_BLOCK,
+      P.blocks_per_wg,         (uint32_t)P.max_chain,  (uint32_t)P.nice_len,    (uint32_t)P.skip_len,
+      (uint32_t)P.good,        (uint32_t)P.klen,       (uint32_t)P.probe,       (uint32_t)P.too_far,
+      (uint32_t)ZT_DF_P4FAR,   (uint32_t)P.adapt_depth, (uint32_t)P.adapt_thr,  (uint32_t)P.adapt_depth2,
+      (uint32_t)P.adapt_thr2,  (uint32_t)P.mq_thr,     P.nblocks,               k.nwg};
+  memcpy(info, rec, sizeof rec);
   return ZT_OK;
 }
 

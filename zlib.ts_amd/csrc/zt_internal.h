@@ -494,6 +494,23 @@ std::vector<int> batch_devices();                                     // zt_set_
 // match kernel that measured their candidates through the queues (out[0]) and
 // at once (out[1]) since the last call; reads and clears the device counter
 extern "C" int zt_debug_match_modes(uint64_t out[2]);
+// debug (deflate.hip): the match stage's result for one stream, n > 0 bytes at
+// in + halo with halo <= 32768 bytes of history in front (in holds halo + n
+// bytes; `level` as zt_deflate_opts.level, compressionType DYNAMIC).  Runs what
+// deflate_dev_run runs up to and including match_kernel -- the same geometry,
+// scratch, parameters (environment hooks included) and launches
+// (deflate_stream_call, deflate_match_launch) -- over a res filled with
+// 0xFFFFFFFF (length 511, which no position can hold: a position the kernel
+// never wrote stays visible).  res[n]: the per-position match words
+// (res_pack); store[ceil(n / DF_BLOCK)]: classify_kernel's flags (a flagged
+// block's positions are not searched); info[kDebugMatchInfo]: the constants
+// and the parameters the call used, in this order: DF_BLOCK, DF_SUB,
+// DF_MAXDIST, segment bytes, blocks per workgroup, max_chain, nice_len,
+// skip_len, good, klen, probe, too_far, ZT_DF_P4FAR, adapt_depth, adapt_thr,
+// adapt_depth2, adapt_thr2, mq_thr, blocks, match workgroups
+constexpr int kDebugMatchInfo = 20;
+extern "C" int zt_debug_match(const uint8_t *in, size_t n, size_t halo, int level, uint32_t *res, uint8_t *store,
+                              uint32_t *info);
 // debug (deflate.hip): match workgroups that changed their chain heads from
 // u32 to u16 (out[0]) and from u16 to u32 (out[1]) since the last call; reads
 // and clears the device counter

@@ -194,6 +194,7 @@ def _load():
         # debug (csrc/zt_internal.h)
         "zt_debug_match_modes": ([P(ctypes.c_uint64)], ctypes.c_int),
         "zt_debug_head_formats": ([P(ctypes.c_uint64)], ctypes.c_int),
+        "zt_debug_match": ([vp, sz, sz, ctypes.c_int, vp, vp, vp], ctypes.c_int),
         "zt_debug_huffman": ([vp, u32, u32, u32, vp, vp], ctypes.c_int),
         "zt_debug_chain": ([vp, vp, vp, u32, ctypes.c_uint64, ctypes.c_uint64, u32, vp, vp, vp], ctypes.c_int),
         "zt_debug_chain_host": ([vp, vp, vp, u32, vp, vp, vp, P(u32), P(ctypes.c_int)], ctypes.c_int),
@@ -1711,6 +1712,34 @@ def debug_head_formats():
     v = (ctypes.c_uint64 * 2)()
     _check(lib.zt_debug_head_formats(v))
     return int(v[0]), int(v[1])
+
+
+# the record zt_debug_match fills, in its order (csrc/zt_internal.h)
+DEBUG_MATCH_INFO = ("block", "sub", "maxdist", "segment", "blocks_per_wg", "max_chain", "nice_len", "skip_len", "good",
+                    "klen", "probe", "too_far", "p4far", "adapt_depth", "adapt_thr", "adapt_depth2", "adapt_thr2",
+                    "mq_thr", "nblocks", "nwg")
+
+
+def debug_match(data, level=6, halo=0):
+    """The deflate match stage's result for `data` (the first `halo` <= 32768
+    bytes are history in front of the stream, not positions): what deflate_raw
+    (DYNAMIC) runs up to and including match_kernel, environment hooks
+    included.  Returns (res, store, info): res uint32[n], per position
+    byte << 24 | len << 15 | dist, 0xFFFFFFFF where the kernel wrote nothing;
+    store uint8[blocks], classify_kernel's flags; info: a dict of the
+    constants and parameters the call used (DEBUG_MATCH_INFO)."""
+    import numpy as np
+
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = buf.size - halo
+    if n <= 0 or halo < 0:
+        raise ValueError("debug_match needs at least one byte after the halo")
+    res = np.zeros(n, dtype=np.uint32)
+    info = np.zeros(len(DEBUG_MATCH_INFO), dtype=np.uint32)
+    store = np.zeros(n // 4096 + 2, dtype=np.uint8)  # (room whatever the build's block size: a block holds sub-chunks)
+    _check(lib.zt_debug_match(buf.ctypes.data, n, halo, level, res.ctypes.data, store.ctypes.data, info.ctypes.data))
+    d = {k: int(v) for k, v in zip(DEBUG_MATCH_INFO, info)}
+    return res, store[:d["nblocks"]], d
 
 
 def debug_huffman(freqs, n, limit):
