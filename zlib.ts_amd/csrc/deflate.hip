@@ -142,14 +142,17 @@ struct ClassifyShared {
 };
 
 // 4 stream bytes at g + off (off >= 0 relative to a possibly unaligned g);
-// bytes at or past `end` read as 0
-__device__ __forceinline__ uint32_t cl_gword(const uint8_t *g, int64_t off, uint64_t end) {
+// bytes at or past `end`, and bytes before `begin`, read as 0 (begin: the
+// window's first byte where off may lie below it -- the inserts' words start
+// at a multiple of 4 at or below a window that starts 1..3 bytes into a halo,
+// and nothing in front of the halo belongs to the caller's buffer)
+__device__ __forceinline__ uint32_t cl_gword(const uint8_t *g, int64_t off, uint64_t end, int64_t begin = 0) {
   const uint8_t *a = g + off;
-  if ((reinterpret_cast<uintptr_t>(a) & 3) == 0 && off + 4 <= (int64_t)end)
+  if ((reinterpret_cast<uintptr_t>(a) & 3) == 0 && off >= begin && off + 4 <= (int64_t)end)
     return *reinterpret_cast<const uint32_t *>(a);
   uint32_t v = 0;
   for (int k = 0; k < 4; ++k)
-    if (off + k < (int64_t)end) v |= (uint32_t)a[k] << (8 * k);
+    if (off + k >= begin && off + k < (int64_t)end) v |= (uint32_t)a[k] << (8 * k);
   return v;
 }
 // 4 bytes at offset wo of the window [dictionary tail dt[0 .. dlen) | stream
@@ -256,7 +259,7 @@ __device__ __forceinline__ void classify_body(const DeflateParams P, const DictV
         const int64_t a = a4 + 16 * (int64_t)(t + 256 * i);
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-          w[i][j] = dfirst ? cl_dword(dtail, dlen, g, lo, n, 16 * (t + 256 * i) + 4 * j) : cl_gword(g, a + 4 * j, n);
+          w[i][j] = dfirst ? cl_dword(dtail, dlen, g, lo, n, 16 * (t + 256 * i) + 4 * j) : cl_gword(g, a + 4 * j, n, h0);
       }
     }
     __syncthreads();  // (the table's EMPTY stores before any insert)
@@ -1745,9 +1748,11 @@ size_t deflate_bound_bytes(size_t n) {
 // the block count and the scratch.  The callers add their stream(s): base,
 // halo, end, final_, the work split (blocks_per_wg, big_wgs, tail_k),
 // restart and span.
+// (level: resolve_opts', the strategy above the level's bits)
 static DeflateParams deflate_params(int level, int ctype, uint32_t nblocks, const DeflateScratch &S, uint8_t *d_out) {
-  const DeflateLevel L = level_params(level);
+  const DeflateLevel L = level_params(level_plain(level));
   DeflateParams P{};
+  P.strategy = level_strategy(level);
   P.nblocks = nblocks;
   P.hist_max = DF_HIST;
   P.max_chain = L.max_chain;
@@ -1786,6 +1791,7 @@ static DeflateParams deflate_params(int level, int ctype, uint32_t nblocks, cons
 // _dict kernels).  res holds every searched position's match word afterwards
 // (zt_debug_match stops here).
 static int deflate_match_launch(DeviceCtx *c, const DeflateParams &P, uint32_t nwg, const DictView *D, hipStream_t s) {
+  if (P.strategy && D) return set_error(ZT_E_INTERNAL, "deflate: a strategy with a dictionary");
   ZT_HIP(hipMemsetAsync(P.nstore, 0, 8, s));
   if (P.store) {
     if (D)
@@ -1795,11 +1801,15 @@ static int deflate_match_launch(DeviceCtx *c, const DeflateParams &P, uint32_t n
     ZT_HIP(hipGetLastError());
   }
   ZT_TRY(timing_begin(c, s, 0));
-  if (D)
-    match_dict_kernel<<<nwg, DF_THREADS, 0, s>>>(P, *D);
-  else
-    match_kernel<<<nwg, DF_THREADS, 0, s>>>(P);
-  ZT_HIP(hipGetLastError());
+  if (P.strategy) {
+    ZT_TRY(deflate_strategy_launch(P, s));
+  } else {
+    if (D)
+      match_dict_kernel<<<nwg, DF_THREADS, 0, s>>>(P, *D);
+    else
+      match_kernel<<<nwg, DF_THREADS, 0, s>>>(P);
+    ZT_HIP(hipGetLastError());
+  }
   ZT_TRY(timing_end(c, s, 0));
   return ZT_OK;
 }
@@ -1981,8 +1991,15 @@ extern "C" int zt_debug_match_modes(uint64_t out[2]) {
 // the match stage's result for one stream (zt_internal.h)
 extern "C" int zt_debug_match(const uint8_t *in, size_t n, size_t halo, int level, uint32_t *res, uint8_t *store,
                               uint32_t *info) {
+  return zt_debug_match_strategy(in, n, halo, level, 0, res, store, info);
+}
+
+extern "C" int zt_debug_match_strategy(const uint8_t *in, size_t n, size_t halo, int level, int strategy,
+                                       uint32_t *res, uint8_t *store, uint32_t *info) {
   if (!in || !res || !store || !info || n == 0 || halo > 32768)
     return set_error(ZT_E_ARG, "zt_debug_match: bad argument");
+  ZT_TRY(strategy_check(strategy));
+  const StrategyScope scope(strategy);
   DeviceCtx *c;
   ZT_TRY(get_ctx(&c));
   std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/zt_index.h"
+#include "../../include/zt_strategy.h"
 #include "zt_internal.h"
 
 using namespace zt;
@@ -90,6 +91,15 @@ int zt_deflate_plan_create(size_t max_n, const zt_deflate_opts *opts, zt_deflate
     return hip_fail(e, "hipMalloc(deflate scratch)");
   }
   *plan = p;
+  return ZT_OK;
+}
+
+// (include/zt_strategy.h) the plan's level is resolve_opts': the strategy
+// goes where that would have put it
+int zt_deflate_plan_set_strategy(zt_deflate_plan *plan, int strategy) {
+  if (!plan) return set_error(ZT_E_ARG, "null plan");
+  ZT_TRY(strategy_check(strategy));
+  plan->level = level_with_strategy(level_plain(plan->level), strategy);
   return ZT_OK;
 }
 

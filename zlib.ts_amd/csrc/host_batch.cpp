@@ -5,13 +5,27 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "../../include/zt_strategy.h"
 #include "zt_internal.h"
 
 namespace zt {
 
+static thread_local int t_strategy = ZT_STRATEGY_DEFAULT;
+
+StrategyScope::StrategyScope(int strategy) : prev_(t_strategy) { t_strategy = strategy; }
+StrategyScope::~StrategyScope() { t_strategy = prev_; }
+
+int strategy_check(int strategy) {
+  if (strategy == ZT_STRATEGY_DEFAULT || strategy == ZT_STRATEGY_HUFFMAN_ONLY || strategy == ZT_STRATEGY_RLE)
+    return ZT_OK;
+  return set_error(ZT_E_ARG, "invalid strategy: " + std::to_string(strategy));
+}
+
 int resolve_opts(const zt_deflate_opts *o, int *ctype, int *level) {
   const int rc = resolve_deflate_opts(o, ctype, level);
-  return rc ? set_error(rc, "invalid compression type") : ZT_OK;
+  if (rc) return set_error(rc, "invalid compression type");
+  *level = level_with_strategy(*level, t_strategy);
+  return ZT_OK;
 }
 
 std::vector<int> fanout_devices(size_t count) {

@@ -398,6 +398,10 @@ struct DeflateParams {
   // selects and publish their progress without draining their LDS queue; 0:
   // the former link throughout (ZT_DF_LINK=0; the streams do not depend on it)
   int link;
+  // the producer of res (include/zt_strategy.h): 0: match_kernel, else
+  // ZT_STRATEGY_RLE / ZT_STRATEGY_HUFFMAN_ONLY: strategy_kernel
+  // (deflate_strategy.hip), which reads none of the search parameters above
+  int strategy;
   // batch of independent streams (zt_deflate_batch_dev): stream f occupies
   // whole blocks from a 32 KiB-aligned offset; per block the [start, end) of
   // its stream (relative to halo = 0), or null for one stream of n bytes
@@ -511,6 +515,17 @@ extern "C" int zt_debug_match_modes(uint64_t out[2]);
 constexpr int kDebugMatchInfo = 20;
 extern "C" int zt_debug_match(const uint8_t *in, size_t n, size_t halo, int level, uint32_t *res, uint8_t *store,
                               uint32_t *info);
+// debug (deflate.hip): zt_debug_match with a strategy (include/zt_strategy.h):
+// the same contract and the same info record; with ZT_STRATEGY_RLE or
+// ZT_STRATEGY_HUFFMAN_ONLY the launch is strategy_kernel's, exactly as the
+// strategy calls launch it (it writes flagged blocks too: no word stays
+// 0xFFFFFFFF); ZT_E_ARG for any other strategy
+extern "C" int zt_debug_match_strategy(const uint8_t *in, size_t n, size_t halo, int level, int strategy,
+                                       uint32_t *res, uint8_t *store, uint32_t *info);
+// The strategies' producer of res (deflate_strategy.hip), launched by
+// deflate_match_launch in place of match_kernel when P.strategy != 0: one
+// workgroup per block, every block written (flagged ones too)
+int deflate_strategy_launch(const DeflateParams &P, hipStream_t s);
 // debug (deflate.hip): match workgroups that changed their chain heads from
 // u32 to u16 (out[0]) and from u16 to u32 (out[1]) since the last call; reads
 // and clears the device counter
@@ -1029,8 +1044,28 @@ struct AuxWait {
   ~AuxWait() { (void)hipStreamSynchronize(s); }
 };
 inline size_t deflate_out_bound(int ctype, size_t n) { return deflate_out_bound(ctype, n, deflate_bound_bytes(n)); }
-// resolve_deflate_opts with the reference's message set
+// resolve_deflate_opts with the reference's message set.  The internal level
+// it returns carries the calling thread's strategy (StrategyScope) above the
+// level's four bits: every call site passes the (ctype, level) pair on as it
+// is, and deflate_params -- the one reader -- takes the two apart again.
 int resolve_opts(const zt_deflate_opts *o, int *ctype, int *level);
+inline int level_with_strategy(int level, int strategy) { return (level & 15) | (strategy << 4); }
+inline int level_plain(int level) { return level & 15; }
+inline int level_strategy(int level) { return level >> 4; }
+// ZT_E_ARG "invalid strategy: N" unless `strategy` is one of include/zt_strategy.h's
+int strategy_check(int strategy);
+// The strategy entry points (strategy_api.cpp) are the plain ones run inside
+// this scope: resolve_opts on this thread hands out levels with the strategy.
+class StrategyScope {
+ public:
+  explicit StrategyScope(int strategy);
+  ~StrategyScope();
+  StrategyScope(const StrategyScope &) = delete;
+  StrategyScope &operator=(const StrategyScope &) = delete;
+
+ private:
+  int prev_;
+};
 // The batch devices a call of `count` items spreads over: the first
 // min(devices, count) of batch_devices(), at least one.
 std::vector<int> fanout_devices(size_t count);

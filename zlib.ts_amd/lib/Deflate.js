@@ -1,7 +1,7 @@
 // zlib Deflate with the reference's surface (src/Deflate.ts:16-99): CMF/FLG
 // (FLEVEL = compressionType), raw DEFLATE and the big-endian Adler-32, built
 // by libzt (zt_zlib_compress) from one device copy of the input.
-import native, { dflt, refError } from './native.js';
+import native, { dflt, refError, strategyAlone } from './native.js';
 import { CompressionType } from './Constants.js';
 
 export class Deflate {
@@ -11,6 +11,8 @@ export class Deflate {
         this.compressionType = dflt(opts.compressionType, CompressionType.DYNAMIC);
         this.lazy = dflt(opts.lazy, 0);
         this.level = dflt(opts.level, 6);
+        // this build's extra option: Strategy.RLE / Strategy.HUFFMAN_ONLY (include/zt_strategy.h)
+        this.strategy = opts.strategy == null ? undefined : opts.strategy;
         // preset dictionary (Uint8Array), named as in Node's zlib; this build's
         // extra option: the reference has none
         this.dictionary = opts.dictionary == null ? undefined
@@ -31,6 +33,7 @@ export class Deflate {
     compress() {
         let r;
         try {
+            strategyAlone(this.strategy, this.dictionary, this.buildIndex);
             if (this.buildIndex) {
                 if (this.dictionary !== undefined) {
                     const err = new Error('an indexed stream cannot use a preset dictionary');
@@ -40,7 +43,7 @@ export class Deflate {
                 r = native.zlibCompressIndexed(this.input, this.compressionType, this.lazy, this.level);
                 this.streamIndex = r.index;
             } else {
-                r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level, this.dictionary);
+                r = native.zlibCompress(this.input, this.compressionType, this.lazy, this.level, this.dictionary, this.strategy);
             }
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';

@@ -3,7 +3,7 @@
 // crc32, flags, filename, comment, deflateOptions) and return value.  The
 // member is built by libzt (zt_gzip_compress): one upload of the input feeds
 // both the GPU deflate pipeline and the GPU CRC-32.
-import native, { dflt, refError } from './native.js';
+import native, { dflt, refError, strategyAlone } from './native.js';
 import { CompressionType } from './Constants.js';
 
 export const GZipMagicNumber = [0x1f, 0x8b];
@@ -58,11 +58,14 @@ export class GZip {
         const o = this.deflateOptions;
         const ct = dflt(o.compressionType, CompressionType.DYNAMIC);
         const mtime = dflt(this.mtime, Math.floor(Date.now() / 1000));
+        // engine extension: deflateOptions.strategy (include/zt_strategy.h)
+        const strategy = o.strategy == null ? undefined : o.strategy;
         let r;
         try {
+            strategyAlone(strategy, undefined, this.buildIndex);
             r = (this.buildIndex ? native.gzipCompressIndexed : native.gzipCompress)(d, ct, dflt(o.lazy, 0), dflt(o.level, 6),
                 this.flags.fname ? headerBytes(this.filename) : null,
-                this.flags.fcomment ? headerBytes(this.comment) : null, !!this.flags.fhcrc, mtime >>> 0);
+                this.flags.fcomment ? headerBytes(this.comment) : null, !!this.flags.fhcrc, mtime >>> 0, strategy);
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';  // src/RawDeflate.ts:110 throws a string
             throw refError(e);

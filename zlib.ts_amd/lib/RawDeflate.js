@@ -1,15 +1,17 @@
 // RawDeflate with the reference's surface (src/RawDeflate.ts:43-114): same
 // constructor options, public fields and return value; the compression runs in
 // libzt on the GPU (zt_deflate_raw).  `level` (1..9, default 6) is this
-// build's extra option; the reference has none.  So is `buildIndex: true`:
+// build's extra option; the reference has none.  So are `strategy`
+// (Strategy.RLE / Strategy.HUFFMAN_ONLY, include/zt_strategy.h: the stream
+// comes from zt_deflate_raw_strategy) and `buildIndex: true`:
 // compress() then also leaves the stream's range index (include/zt_index.h,
 // the blob RawInflate.decompressRange takes) in `streamIndex`, written with the
 // stream instead of by a second decode; its positions count from the start of
 // the returned buffer, so with `outputIndex` the caller's prefix is in front.
-import native, { dflt, refError } from './native.js';
-import { CompressionType, DefaultDeflateBufferSize } from './Constants.js';
+import native, { dflt, refError, strategyAlone } from './native.js';
+import { CompressionType, DefaultDeflateBufferSize, Strategy } from './Constants.js';
 
-export { CompressionType };
+export { CompressionType, Strategy };
 
 export class RawDeflate {
     constructor(input, opts = {}) {
@@ -17,6 +19,7 @@ export class RawDeflate {
         this.lazy = dflt(opts.lazy, 0);
         this.compressionType = dflt(opts.compressionType, CompressionType.DYNAMIC);
         this.level = dflt(opts.level, 6);
+        this.strategy = opts.strategy == null ? undefined : opts.strategy;
         // preset dictionary (Uint8Array), named as in Node's zlib; this build's
         // extra option: the reference has none
         this.dictionary = opts.dictionary == null ? undefined
@@ -43,6 +46,7 @@ export class RawDeflate {
         }
         let stream;
         try {
+            strategyAlone(this.strategy, this.dictionary, this.buildIndex);
             if (this.buildIndex) {
                 if (this.dictionary !== undefined) {
                     const err = new Error('an indexed stream cannot use a preset dictionary');
@@ -53,7 +57,7 @@ export class RawDeflate {
                 stream = r.output;
                 this.streamIndex = r.index;
             } else {
-                stream = native.deflateRaw(this.input, ct, this.lazy, this.level, this.dictionary);
+                stream = native.deflateRaw(this.input, ct, this.lazy, this.level, this.dictionary, this.strategy);
             }
         } catch (e) {
             if (e.ztStatus === -1) throw 'invalid compression type';

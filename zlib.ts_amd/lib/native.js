@@ -30,6 +30,16 @@ export function dflt(v, d) {
     return v === undefined || v === null ? d : v;
 }
 
+// a strategy goes alone: not with a preset dictionary, not with buildIndex
+export function strategyAlone(strategy, dictionary, buildIndex) {
+    if (strategy === undefined) return;
+    if (dictionary !== undefined || buildIndex) {
+        const err = new Error('a strategy cannot be combined with a dictionary or an index');
+        err.ztStatus = -103;
+        throw err;
+    }
+}
+
 // libzt's message is the reference's text; keep the status code beside it
 export function refError(e) {
     const err = new Error(e.message);

@@ -20,6 +20,7 @@
 #include "../../include/zt_bgzf.h"
 #include "../../include/zt_stream.h"
 #include "../../include/zt_stream_container.h"
+#include "../../include/zt_strategy.h"
 
 namespace {
 
@@ -131,6 +132,17 @@ bool get_dict(napi_env env, napi_value v, const uint8_t **p, size_t *n, bool *gi
   return true;
 }
 
+// optional trailing `strategy` argument (include/zt_strategy.h): undefined /
+// null = none, the plain entry point
+bool get_strategy(napi_env env, napi_value v, int *strategy) {
+  napi_valuetype t;
+  napi_typeof(env, v, &t);
+  *strategy = 0;
+  if (t == napi_undefined || t == napi_null) return false;
+  *strategy = (int)get_i64(env, v, 0);
+  return true;
+}
+
 // crc32Update(data: Uint8Array, crc: number) -> number
 napi_value crc32_update(napi_env env, napi_callback_info info) {
   napi_value a[2];
@@ -161,10 +173,13 @@ napi_value adler32_update(napi_env env, napi_callback_info info) {
   return r;
 }
 
-// deflateRaw(input: Uint8Array, compressionType, lazy, level[, dictionary]) -> Uint8Array
+// deflateRaw(input: Uint8Array, compressionType, lazy, level[, dictionary[, strategy]]) -> Uint8Array
+// (a strategy goes without a dictionary: the facade refuses the pair)
 napi_value deflate_raw(napi_env env, napi_callback_info info) {
-  napi_value a[5];
-  args(env, info, a, 5);
+  napi_value a[6];
+  args(env, info, a, 6);
+  int strategy;
+  const bool has_s = get_strategy(env, a[5], &strategy);
   const uint8_t *d;
   size_t dn;
   bool has_d;
@@ -178,7 +193,9 @@ napi_value deflate_raw(napi_env env, napi_callback_info info) {
   o.level = (int)get_i64(env, a[3], -1);
   uint8_t *out = nullptr;
   size_t olen = 0;
-  int rc = has_d ? zt_deflate_raw_dict(p, n, &o, d, dn, &out, &olen) : zt_deflate_raw(p, n, &o, &out, &olen);
+  int rc = has_s   ? zt_deflate_raw_strategy(p, n, &o, strategy, &out, &olen)
+           : has_d ? zt_deflate_raw_dict(p, n, &o, d, dn, &out, &olen)
+                   : zt_deflate_raw(p, n, &o, &out, &olen);
   if (rc) return throw_zt(env, rc);
   return new_u8(env, out, olen);
 }
@@ -259,11 +276,13 @@ bool opt_u8(napi_env env, napi_value v, const uint8_t **p, size_t *n, bool *pres
   return !*present || get_u8(env, v, p, n);
 }
 
-// gzipCompress(input, compressionType, lazy, level, name|null, comment|null, hcrc, mtime) -> {output, crc32}
-// (indexed: gzipCompressIndexed, the same arguments -> {output, crc32, index})
+// gzipCompress(input, compressionType, lazy, level, name|null, comment|null, hcrc, mtime[, strategy]) -> {output, crc32}
+// (indexed: gzipCompressIndexed, the first eight arguments -> {output, crc32, index})
 napi_value gzip_compress_any(napi_env env, napi_callback_info info, bool indexed) {
-  napi_value a[8];
-  args(env, info, a, 8);
+  napi_value a[9];
+  args(env, info, a, 9);
+  int strategy;
+  const bool has_s = !indexed && get_strategy(env, a[8], &strategy);
   const uint8_t *p;
   size_t n;
   if (!get_u8(env, a[0], &p, &n)) return nullptr;
@@ -287,6 +306,7 @@ napi_value gzip_compress_any(napi_env env, napi_callback_info info, bool indexed
   size_t olen = 0, ilen = 0;
   uint32_t crc = 0;
   int rc = indexed ? zt_gzip_compress_indexed(p, n, &o, &out, &olen, &crc, &idx, &ilen)
+           : has_s ? zt_gzip_compress_strategy(p, n, &o, strategy, &out, &olen, &crc)
                    : zt_gzip_compress(p, n, &o, &out, &olen, &crc);
   if (rc) return throw_zt(env, rc);
   napi_value obj;
@@ -456,10 +476,13 @@ napi_value zlib_decompress_batch(napi_env env, napi_callback_info info) {
 }
 
 // zlibCompress(input, compressionType, lazy, level) -> {output, adler32}
-// (a fifth argument: the preset dictionary -- FDICT and DICTID in the header)
+// (a fifth argument: the preset dictionary -- FDICT and DICTID in the header;
+// a sixth: the strategy, without a dictionary)
 napi_value zlib_compress(napi_env env, napi_callback_info info) {
-  napi_value a[5];
-  args(env, info, a, 5);
+  napi_value a[6];
+  args(env, info, a, 6);
+  int strategy;
+  const bool has_s = get_strategy(env, a[5], &strategy);
   const uint8_t *d;
   size_t dn;
   bool has_d;
@@ -474,8 +497,9 @@ napi_value zlib_compress(napi_env env, napi_callback_info info) {
   uint8_t *out = nullptr;
   size_t olen = 0;
   uint32_t adler = 1;
-  int rc = has_d ? zt_zlib_compress_dict(p, n, &o, d, dn, &out, &olen, &adler)
-                 : zt_zlib_compress(p, n, &o, &out, &olen, &adler);
+  int rc = has_s   ? zt_zlib_compress_strategy(p, n, &o, strategy, &out, &olen, &adler)
+           : has_d ? zt_zlib_compress_dict(p, n, &o, d, dn, &out, &olen, &adler)
+                   : zt_zlib_compress(p, n, &o, &out, &olen, &adler);
   if (rc) return throw_zt(env, rc);
   napi_value obj;
   napi_create_object(env, &obj);

@@ -274,6 +274,18 @@ def _load():
         "zt_container_session_get_info": ([vp, P(ContainerSessionInfo)], ctypes.c_int),
         "zt_container_session_member": ([vp, sz, P(ContainerMember)], ctypes.c_int),
         "zt_container_session_message": ([vp], ctypes.c_char_p),
+        # include/zt_strategy.h
+        "zt_deflate_raw_strategy": ([vp, sz, P(DeflateOpts), ctypes.c_int, u8pp, P(sz)], ctypes.c_int),
+        "zt_deflate_raw_batch_strategy": ([P(vp), P(sz), sz, P(DeflateOpts), ctypes.c_int, u8pp, P(sz),
+                                          P(ctypes.c_int)], ctypes.c_int),
+        "zt_zlib_compress_strategy": ([vp, sz, P(DeflateOpts), ctypes.c_int, u8pp, P(sz), P(u32)], ctypes.c_int),
+        "zt_gzip_compress_strategy": ([vp, sz, P(GzipOpts), ctypes.c_int, u8pp, P(sz), P(u32)], ctypes.c_int),
+        "zt_zlib_compress_batch_strategy": ([P(vp), P(sz), sz, P(DeflateOpts), ctypes.c_int, u8pp, P(sz),
+                                            P(ctypes.c_int)], ctypes.c_int),
+        "zt_gzip_compress_batch_strategy": ([P(vp), P(sz), sz, P(GzipOpts), ctypes.c_int, u8pp, P(sz),
+                                            P(ctypes.c_int)], ctypes.c_int),
+        "zt_deflate_plan_set_strategy": ([vp, ctypes.c_int], ctypes.c_int),
+        "zt_debug_match_strategy": ([vp, sz, sz, ctypes.c_int, ctypes.c_int, vp, vp, vp], ctypes.c_int),  # debug
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name, None)
@@ -366,6 +378,21 @@ CONTAINER_STREAM_SYMBOLS = [
 SESSION_AUTO, SESSION_GZIP, SESSION_ZLIB = 0, 1, 2
 
 
+# every symbol include/zt_strategy.h declares (checked by tests/test_strategy_ref.py)
+STRATEGY_SYMBOLS = [
+    "zt_deflate_raw_strategy", "zt_deflate_raw_batch_strategy", "zt_zlib_compress_strategy",
+    "zt_gzip_compress_strategy", "zt_zlib_compress_batch_strategy", "zt_gzip_compress_batch_strategy",
+    "zt_deflate_plan_set_strategy",
+]
+# zlib's numbers; strategy=None in the calls below is the plain entry point
+STRATEGY_DEFAULT, STRATEGY_HUFFMAN_ONLY, STRATEGY_RLE = 0, 2, 3
+
+
+def _no_dictionary(strategy, dictionary):
+    if strategy is not None and dictionary is not None:
+        raise ValueError("a strategy cannot be combined with a dictionary")
+
+
 def _check(rc):
     if rc != ZT_OK:
         raise ZtError(rc, lib.zt_last_error_message().decode(errors="replace"))
@@ -410,13 +437,17 @@ def checksums(data, crc=0, adler=1):
     return c.value, a.value
 
 
-def deflate_raw(data, compression_type=2, lazy=0, level=-1, dictionary=None):
-    """dictionary: preset dictionary (zlib's zdict), include/zt_dict.h."""
+def deflate_raw(data, compression_type=2, lazy=0, level=-1, dictionary=None, strategy=None):
+    """dictionary: preset dictionary (zlib's zdict), include/zt_dict.h.
+    strategy: STRATEGY_RLE / STRATEGY_HUFFMAN_ONLY (include/zt_strategy.h)."""
+    _no_dictionary(strategy, dictionary)
     b, n = _cbuf(data)
     opts = DeflateOpts(compression_type, lazy, level)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
-    if dictionary is not None:
+    if strategy is not None:
+        _check(lib.zt_deflate_raw_strategy(b, n, ctypes.byref(opts), strategy, ctypes.byref(out), ctypes.byref(olen)))
+    elif dictionary is not None:
         d, dn = _cbuf(dictionary)
         _check(lib.zt_deflate_raw_dict(b, n, ctypes.byref(opts), d, dn, ctypes.byref(out), ctypes.byref(olen)))
     else:
@@ -741,7 +772,8 @@ def inflate_raw_batch(streams, ref_strict=False, dictionary=None):
     return res
 
 
-def deflate_raw_batch(items, compression_type=2, level=-1, dictionary=None):
+def deflate_raw_batch(items, compression_type=2, level=-1, dictionary=None, strategy=None):
+    _no_dictionary(strategy, dictionary)
     k = len(items)
     bufs = [_cbuf(s) for s in items]
     ptrs = (ctypes.c_void_p * k)(*[ctypes.addressof(b) for b, _ in bufs])
@@ -750,7 +782,9 @@ def deflate_raw_batch(items, compression_type=2, level=-1, dictionary=None):
     olens = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
     opts = DeflateOpts(compression_type, 0, level)
-    if dictionary is not None:
+    if strategy is not None:
+        rc = lib.zt_deflate_raw_batch_strategy(ptrs, lens, k, ctypes.byref(opts), strategy, outs, olens, st)
+    elif dictionary is not None:
         d, dn = _cbuf(dictionary)
         rc = lib.zt_deflate_raw_batch_dict(ptrs, lens, k, ctypes.byref(opts), d, dn, outs, olens, st)
     else:
@@ -769,7 +803,8 @@ def _take(out, olen):
     return res
 
 
-def gzip_compress(data, name=None, comment=None, hcrc=False, mtime=0, compression_type=2, lazy=0, level=-1):
+def gzip_compress(data, name=None, comment=None, hcrc=False, mtime=0, compression_type=2, lazy=0, level=-1,
+                  strategy=None):
     """GZip.compress (src/GZip.ts:96-194); name/comment are header bytes.
     Returns (member bytes, crc32)."""
     b, n = _cbuf(data)
@@ -783,7 +818,11 @@ def gzip_compress(data, name=None, comment=None, hcrc=False, mtime=0, compressio
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     crc = ctypes.c_uint32()
-    _check(lib.zt_gzip_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(crc)))
+    if strategy is not None:
+        _check(lib.zt_gzip_compress_strategy(b, n, ctypes.byref(o), strategy, ctypes.byref(out), ctypes.byref(olen),
+                                             ctypes.byref(crc)))
+    else:
+        _check(lib.zt_gzip_compress(b, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(olen), ctypes.byref(crc)))
     return _take(out, olen), crc.value
 
 
@@ -804,7 +843,8 @@ def _batch_take(k, outs, olens):
     return res
 
 
-def gzip_compress_batch(items, name=None, comment=None, hcrc=False, mtime=0, compression_type=2, lazy=0, level=-1):
+def gzip_compress_batch(items, name=None, comment=None, hcrc=False, mtime=0, compression_type=2, lazy=0, level=-1,
+                        strategy=None):
     """GZip members of many buffers in one pipeline per device (config C4)."""
     bs, ptrs, lens = _batch_ptrs(items)
     k = len(bs)
@@ -818,18 +858,24 @@ def gzip_compress_batch(items, name=None, comment=None, hcrc=False, mtime=0, com
     outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
     olens = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
-    _check(lib.zt_gzip_compress_batch(ptrs, lens, k, ctypes.byref(o), outs, olens, st))
+    if strategy is not None:
+        _check(lib.zt_gzip_compress_batch_strategy(ptrs, lens, k, ctypes.byref(o), strategy, outs, olens, st))
+    else:
+        _check(lib.zt_gzip_compress_batch(ptrs, lens, k, ctypes.byref(o), outs, olens, st))
     return _batch_take(k, outs, olens)
 
 
-def zlib_compress_batch(items, compression_type=2, lazy=0, level=-1, dictionary=None):
+def zlib_compress_batch(items, compression_type=2, lazy=0, level=-1, dictionary=None, strategy=None):
+    _no_dictionary(strategy, dictionary)
     bs, ptrs, lens = _batch_ptrs(items)
     k = len(bs)
     opts = DeflateOpts(compression_type, lazy, level)
     outs = (ctypes.POINTER(ctypes.c_uint8) * k)()
     olens = (ctypes.c_size_t * k)()
     st = (ctypes.c_int * k)()
-    if dictionary is not None:
+    if strategy is not None:
+        _check(lib.zt_zlib_compress_batch_strategy(ptrs, lens, k, ctypes.byref(opts), strategy, outs, olens, st))
+    elif dictionary is not None:
         d, dn = _cbuf(dictionary)
         _check(lib.zt_zlib_compress_batch_dict(ptrs, lens, k, ctypes.byref(opts), d, dn, outs, olens, st))
     else:
@@ -1004,15 +1050,19 @@ def gunzip(data):
     return res, members
 
 
-def zlib_compress(data, compression_type=2, lazy=0, level=-1, dictionary=None):
+def zlib_compress(data, compression_type=2, lazy=0, level=-1, dictionary=None, strategy=None):
     """Deflate.compress (src/Deflate.ts:60-99).  Returns (stream, adler32).
     dictionary: the stream carries FDICT and the dictionary's Adler-32."""
+    _no_dictionary(strategy, dictionary)
     b, n = _cbuf(data)
     o = DeflateOpts(compression_type, lazy, level)
     out = ctypes.POINTER(ctypes.c_uint8)()
     olen = ctypes.c_size_t()
     adler = ctypes.c_uint32()
-    if dictionary is not None:
+    if strategy is not None:
+        _check(lib.zt_zlib_compress_strategy(b, n, ctypes.byref(o), strategy, ctypes.byref(out), ctypes.byref(olen),
+                                             ctypes.byref(adler)))
+    elif dictionary is not None:
         d, dn = _cbuf(dictionary)
         _check(lib.zt_zlib_compress_dict(b, n, ctypes.byref(o), d, dn, ctypes.byref(out), ctypes.byref(olen),
                                          ctypes.byref(adler)))
@@ -1493,10 +1543,16 @@ def dev_checksums(ptr, n, crc=0, adler=1, stream=None):
 
 
 class DeflatePlan:
-    def __init__(self, max_n, level=-1, compression_type=2):
+    def __init__(self, max_n, level=-1, compression_type=2, strategy=None):
         self.h = ctypes.c_void_p()
         opts = DeflateOpts(compression_type, 0, level)
         _check(lib.zt_deflate_plan_create(max_n, ctypes.byref(opts), ctypes.byref(self.h)))
+        if strategy is not None:
+            self.set_strategy(strategy)
+
+    def set_strategy(self, strategy):
+        """The strategy of every later run (include/zt_strategy.h)."""
+        _check(lib.zt_deflate_plan_set_strategy(self.h, strategy))
 
     def run(self, d_in, n, d_out, halo=0, final=1, stream=None):
         olen = ctypes.c_size_t()
@@ -1720,7 +1776,13 @@ DEBUG_MATCH_INFO = ("block", "sub", "maxdist", "segment", "blocks_per_wg", "max_
                     "mq_thr", "nblocks", "nwg")
 
 
-def debug_match(data, level=6, halo=0):
+def debug_match_strategy(data, strategy, level=6, halo=0):
+    """debug_match with a strategy (zt_debug_match_strategy): what the
+    strategy calls launch in place of match_kernel.  Same returns."""
+    return debug_match(data, level, halo, strategy)
+
+
+def debug_match(data, level=6, halo=0, strategy=None):
     """The deflate match stage's result for `data` (the first `halo` <= 32768
     bytes are history in front of the stream, not positions): what deflate_raw
     (DYNAMIC) runs up to and including match_kernel, environment hooks
@@ -1737,7 +1799,12 @@ def debug_match(data, level=6, halo=0):
     res = np.zeros(n, dtype=np.uint32)
     info = np.zeros(len(DEBUG_MATCH_INFO), dtype=np.uint32)
     store = np.zeros(n // 4096 + 2, dtype=np.uint8)  # (room whatever the build's block size: a block holds sub-chunks)
-    _check(lib.zt_debug_match(buf.ctypes.data, n, halo, level, res.ctypes.data, store.ctypes.data, info.ctypes.data))
+    if strategy is not None:
+        _check(lib.zt_debug_match_strategy(buf.ctypes.data, n, halo, level, strategy, res.ctypes.data,
+                                           store.ctypes.data, info.ctypes.data))
+    else:
+        _check(lib.zt_debug_match(buf.ctypes.data, n, halo, level, res.ctypes.data, store.ctypes.data,
+                                  info.ctypes.data))
     d = {k: int(v) for k, v in zip(DEBUG_MATCH_INFO, info)}
     return res, store[:d["nblocks"]], d
 
